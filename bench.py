@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X SpMM engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cop20k_k32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cop20k_k32] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps as one region and prints the
+result line (metric, value, unit, higher_is_better, dtype, ms_per_step).
+--full adds everything measured beside that figure: the CPU baseline, nine
+more timed regions (value is then their median), the bind / rebind, warm,
+copy-floor and rocSPARSE legs, the plans timed beside a decomposed step and
+the post-timing result check (exit status 3 when it fails).
+--dump-outputs DIR writes the Y of the last timed step as DIR/Y.npy.
 
 Metric (BASELINE.json): effective GFLOP/s (= 2*nnz*K / t, the reference's
 own formula, results/visualisation_fat_vector.ipynb:1595-1601) and achieved
@@ -68,6 +76,8 @@ def metric_for(config: str, K: int, variant: str) -> str:
 
 STABILIZE_REPLAYS_COLLECTIVE = 10  # the same, as a count every rank replays (graphs with RCCL calls)
 STABILIZE_S = 0.1  # untimed graph replays before the first timed region (clock ramp)
+GRAPH_CHUNK = 4096  # most launches captured into one hipGraph; a longer timed region replays it
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: most bytes written in all
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 MPIEXEC = "/opt/conda/bin/mpiexec"
 
@@ -409,7 +419,7 @@ def _stabilize(g) -> int:
     return reps
 
 
-def vendor_leg(copies, args, timed, flops: float):
+def vendor_leg(copies, steps: int, timed, flops: float):
     """rocSPARSE generic SpMM (the PETSc-block analogue, SC/main.cpp:289-402)
     on the same resident copies, same rotation and graph timing as the
     engine's kernel: the library line beside `value`, not part of it."""
@@ -424,10 +434,10 @@ def vendor_leg(copies, args, timed, flops: float):
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=vs):
-            for i in range(args.steps):
+            for i in range(steps):
                 hs[i % len(hs)].run()
         _stabilize(g)
-        ms = timed(g) / args.steps
+        ms = timed(g) / steps
         return {"library": "rocSPARSE rocsparse_spmm (CSR, f64, row-major, alg default)",
                 "avg_launch_ms": round(ms, 6), "GFLOPs": round(flops / (ms * 1e-3) / 1e9, 3),
                 "timing": "same copies / rotation / hipGraph replay as the engine's kernel"}
@@ -473,6 +483,21 @@ def sampled_check(A, rows, dX, Ydev, exact: bool, row_base: int = 0) -> dict:
             "criterion": "bit-identical" if exact else "|y - y_ref| <= 1e-12 x sum|a||x|",
             "sample": "longest rows, merge-team boundary (carry) rows, empty, first/last, random",
             "seconds": round(time.time() - t0, 1)}
+
+
+def dump_outputs(path: str, Y) -> None:
+    """--dump-outputs DIR: the Y of the last timed step as DIR/Y.npy (float64),
+    whole when it fits DUMP_LIMIT_BYTES, else a fixed sample of its rows
+    (seed 0, ascending), so two builds given the same arguments write
+    arrays that compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    keep = (DUMP_LIMIT_BYTES - 1024) // (8 * Y.shape[1])  # (1 KiB: the .npy header)
+    if Y.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(Y.shape[0], keep, replace=False))
+        Y = Y[torch.from_numpy(rows).to(Y.device)]
+    np.save(os.path.join(path, "Y.npy"), Y.to(torch.float64).cpu().numpy())
 
 
 class Deadline:
@@ -667,19 +692,24 @@ def bench_rowpart(args, world: int, rank: int, local: int, K: int) -> None:
     # eager (the step holds an RCCL collective); ~65 ms per step at N = 1
     dl.enter("timed steps")
     ms_step = _timed_events(lambda: [plan.run(X, Y) for _ in range(args.steps)], world) / args.steps
-    ms_kern = _timed_events(lambda: [plan.run_local(X, Y) for _ in range(args.steps)], world) / args.steps
-    # the reference's own exchange semantics beside it: Gatherv to rank 0
-    # (SC/...RowWise.cpp:85-87) instead of the all-gather
-    plan_root = D.DistPlan(comm, smfv.Variant.ROWWISE, dA, K, to_all=False, rowpart=True, m=m)
-    plan_root.run(X, Y)
-    ms_root = _timed_events(lambda: [plan_root.run(X, Y) for _ in range(args.steps)], world) / args.steps
-    del plan_root
-    # sampled check, outside the timed region: rank 0's rows + rows of the other blocks
-    dl.enter("result check")
-    plan.run(X, Y)
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Y)
+    # --full: the rank-local kernel alone, and the reference's own exchange
+    # semantics beside the step: Gatherv to rank 0 (SC/...RowWise.cpp:85-87)
+    # instead of the all-gather
+    ms_kern = ms_root = 0.0
+    if args.full:
+        ms_kern = _timed_events(lambda: [plan.run_local(X, Y) for _ in range(args.steps)], world) / args.steps
+        plan_root = D.DistPlan(comm, smfv.Variant.ROWWISE, dA, K, to_all=False, rowpart=True, m=m)
+        plan_root.run(X, Y)
+        ms_root = _timed_events(lambda: [plan_root.run(X, Y) for _ in range(args.steps)], world) / args.steps
+        del plan_root
+        # sampled check, outside the timed region: rank 0's rows + rows of the other blocks
+        dl.enter("result check")
+        plan.run(X, Y)
+        torch.cuda.synchronize()
     chk = None
-    if rank == 0:
+    if args.full and rank == 0:
         rows = sampling.sample_rows(A.rowPtr, K, n_random=2000)
         chk = sampled_check(A, rows, X, Y, exact=True, row_base=-r0)
         other_ok, other_n = True, 0
@@ -715,6 +745,7 @@ def bench_rowpart(args, world: int, rank: int, local: int, K: int) -> None:
             "config": {"workload": f"syn80m_k32: {m}x{m} x K={K}, ROWWISE row-partitioned over {world} GPU(s)"
                                    " + RCCL all-gather of Y", "m": m, "n": n, "nnz": nnz_tot, "K": K,
                        "variant": "ROWWISE", "parallelism": f"rows/{world}, X replicated, Y all-gathered"},
+            # (the rank-local kernel is timed alone, and the gather to rank 0, under --full)
             "roofline": {"bound": "hbm", "achieved": round(kbytes / (ms_kern * 1e-3) / 1e9, 1),
                          "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(kbytes / (ms_kern * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
@@ -722,9 +753,10 @@ def bench_rowpart(args, world: int, rank: int, local: int, K: int) -> None:
                          "algorithmic_bytes_per_launch": kbytes,
                          "gather_model_GBps": round(gather_bytes / (ms_kern * 1e-3) / 1e9, 1),
                          "avg_launch_ms": round(ms_kern, 4),
-                         "timing": "HIP events around eager launches (rank-local kernel alone; max over ranks)"},
-            "exchange_ms": round(ms_step - ms_kern, 4),
-            "exchange_ms_gather_to_root": round(ms_root - ms_kern, 4),
+                         "timing": "HIP events around eager launches (rank-local kernel alone; max over ranks)"}
+            if args.full else None,
+            "exchange_ms": round(ms_step - ms_kern, 4) if args.full else None,
+            "exchange_ms_gather_to_root": round(ms_root - ms_kern, 4) if args.full else None,
             "exchange_note": "exchange_ms: all-gather of the Y blocks to every rank (ncclAllGather); "
                              "exchange_ms_gather_to_root: the reference's MPI_Gatherv semantics (grouped "
                              "ncclSend/ncclRecv to rank 0, SC/...RowWise.cpp:85-87); each = (kernel + "
@@ -805,10 +837,11 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
     # to rank 0 only, MPI_Gatherv / MPI_Reduce, SC/...RowWise.cpp:85-87), the
     # other row partition (SMFV_DIST_BALANCED_ROWS) and the chunked exchange
     # (SMFV_DIST_CHUNKS: chunk j's all-gatherv overlapped with chunk j + 1's
-    # compute)
+    # compute); a run without --full times the value's step alone
     kinds = {"value": dict(to_all=True, partition=args.partition)}
-    kinds["gather_to_root"] = dict(to_all=False, partition=args.partition)
-    if rows:
+    if args.full:
+        kinds["gather_to_root"] = dict(to_all=False, partition=args.partition)
+    if rows and args.full:
         other = "reference" if args.partition == "balanced" else "balanced"
         kinds[f"{other}_rows"] = dict(to_all=True, partition=other)
         if args.chunks > 1:
@@ -840,7 +873,9 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
             (plans[key].run_local if local else plans[key].run)(dX, dY)
         return _graph_or_eager(step, args.steps, world)
     ms_step, how = timed_plan("value")
-    ms_loc, how_loc = timed_plan("value", local=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, copies[(args.steps - 1) % ncopies][2])
+    ms_loc, how_loc = timed_plan("value", local=True) if args.full else (0.0, None)
     beside = {}
     for key in kinds:
         if key == "value":
@@ -851,26 +886,27 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
     # correctness after timing: every rank's Y is the whole product (TO_ALL),
     # against the untiled row kernel (pinned to the reference by the tests;
     # not the tiled kernel the ranks' shares run) -- the value's plan and,
-    # for ROWWISE, the other TO_ALL plans
-    dl.enter("result check")
+    # for ROWWISE, the other TO_ALL plans (--full)
     plans, dX, dY = copies[0]
-    ref_plan = smfv.SpmmPlan(smfv.Variant.SEQUENTIAL, plans["value"].A, K, tiles="off")
-    Yseq = torch.empty_like(dY)
-    ref_plan.run(dX, Yseq)
-    ok = True
-    for key, kw in kinds.items():
-        if not kw["to_all"]:
-            continue
-        dY.fill_(float("nan"))
-        plans[key].run(dX, dY)
+    ok, ms_rep, reps = True, 0.0, None
+    if args.full:
+        dl.enter("result check")
+        ref_plan = smfv.SpmmPlan(smfv.Variant.SEQUENTIAL, plans["value"].A, K, tiles="off")
+        Yseq = torch.empty_like(dY)
+        ref_plan.run(dX, Yseq)
+        for key, kw in kinds.items():
+            if not kw["to_all"]:
+                continue
+            dY.fill_(float("nan"))
+            plans[key].run(dX, dY)
+            torch.cuda.synchronize()
+            mabs, _ = smfv.compare(Yseq, dY)
+            ok &= (mabs == 0.0) if variant != "NONZERO" else (mabs <= 1e-6)
+        # secondary: independent copies (every rank its own whole problem)
+        reps = [(smfv.SpmmPlan(V, pl["value"].A, K, tiles=args.tiles), dXc, dYc) for pl, dXc, dYc in copies]
         torch.cuda.synchronize()
-        mabs, _ = smfv.compare(Yseq, dY)
-        ok &= (mabs == 0.0) if variant != "NONZERO" else (mabs <= 1e-6)
-    # secondary: independent copies (every rank its own whole problem)
-    reps = [(smfv.SpmmPlan(V, pl["value"].A, K, tiles=args.tiles), dXc, dYc) for pl, dXc, dYc in copies]
-    torch.cuda.synchronize()
-    ms_rep, _ = _graph_or_eager(lambda i: reps[i % ncopies][0].run(reps[i % ncopies][1], reps[i % ncopies][2]),
-                                args.steps, world)
+        ms_rep, _ = _graph_or_eager(lambda i: reps[i % ncopies][0].run(reps[i % ncopies][1], reps[i % ncopies][2]),
+                                    args.steps, world)
     first, last, _, _ = plans["value"].partition()
     if rows:
         r0, r1 = int(first[rank]), int(last[rank]) + 1
@@ -901,7 +937,8 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
         pr = per_rank.tolist()
         slow = max(range(world), key=lambda r: pr[2 * r])
         s_ms, s_bytes = pr[2 * slow], int(pr[2 * slow + 1])
-        loc_gbps = s_bytes / (s_ms * 1e-3) / 1e9  # the slowest rank's local bytes / its local time (GB/s)
+        # the slowest rank's local bytes / its local time (GB/s)
+        loc_gbps = s_bytes / (s_ms * 1e-3) / 1e9 if s_ms > 0 else 0.0
         traffic, traffic_src = measured_rank_traffic(args.config, world, slow, kernel_label(variant, K, st, 8 * n * K))
         others = {}
         for i, key in enumerate(keys):
@@ -936,7 +973,7 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
                                    "plan under rocprofv3 PMC on one GPU (bench.py --rank-plans N --rank-only r)"},
             "rank_local_ms": round(ms_loc, 6),
             "exchange_ms": round(ms_step - ms_loc, 6),
-            "exchange_ms_gather_to_root": round(others["gather_to_root"]["exchange_ms"], 6),
+            "exchange_ms_gather_to_root": others.get("gather_to_root", {}).get("exchange_ms"),
             "plans_beside": others,
             "exchange_note": "exchange_ms: all-gather of Y to every rank (the value's step); "
                              "plans_beside.gather_to_root: the reference's semantics, blocks gathered to rank 0 "
@@ -951,9 +988,13 @@ def bench_decomposed(args, world: int, rank: int, local: int, kind: str, K: int,
                                                   "(bit-identical; NONZERO 1e-6), every all-gather plan"},
             "replicas": {"note": "every rank its own whole problem, no collective (weak scaling)",
                          "ms_per_step": round(ms_rep, 6),
-                         "value_GFLOPs": round(world * flops / (ms_rep * 1e-3) / 1e9, 3)},
+                         "value_GFLOPs": round(world * flops / (ms_rep * 1e-3) / 1e9, 3) if ms_rep > 0 else None},
             "cpu_baseline": cpu,
+            "full": args.full,
         }
+        if not args.full:  # (not measured: the value's step alone was timed)
+            for k in ("roofline", "rank_local_ms", "exchange_ms", "check", "replicas"):
+                out[k] = None
         print(json.dumps(out))
     del copies, reps, plans
     comm.close()
@@ -1310,7 +1351,19 @@ def main() -> None:
     ap.add_argument("--phase-timeout", type=float, default=240.0,
                     help="multi-GPU paths: seconds a phase (RCCL set-up, plans, warm-up, timing, check) may take "
                          "before a diagnostic JSON line and exit status 4 (0 = no watchdog)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baseline, nine more timed regions (their "
+                         "median, min and max), the bind / rebind, warm, copy-floor and rocSPARSE legs, the plans "
+                         "timed beside a decomposed step, and the post-timing result check.  Without it a run sets "
+                         "up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (Y, on rank 0) as "
+                         "DIR/Y.npy in float64; an output over 64 MB is written as a fixed sample of its rows")
     args = ap.parse_args()
+    if args.dump_outputs and args.rank_plans > 0:
+        ap.error("--dump-outputs: a --rank-plans projection has no one output (every rank's share is timed in turn)")
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_vendor = args.no_warm = args.no_copy_floor = args.no_rebind = True
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
@@ -1401,8 +1454,8 @@ def main() -> None:
         t_plan.append(time.time() - t0)
         copies.append((plan, dX, dY))
     torch.cuda.synchronize()
-    # bind cost (the values snapshot gather of a tiled plan), timed on its own
-    bind_ms = _timed_events(lambda: [copies[0][0].bind_values() for _ in range(20)], 1) / 20
+    # bind cost (the values snapshot gather of a tiled plan), timed on its own (--full)
+    bind_ms = _timed_events(lambda: [copies[0][0].bind_values() for _ in range(20)], 1) / 20 if args.full else None
 
     def step(i: int, warm: bool = False):
         plan, dX, dY = copies[0 if warm else i % ncopies]
@@ -1416,16 +1469,15 @@ def main() -> None:
     # side stream): a ~40 us launch issued from Python + ctypes one by one is
     # host-bound, the graph replay is not.  Inputs stay resident; nothing is
     # skipped: the graph holds exactly `steps` SpMM launches.
-    def capture(warm: bool):
+    def capture(warm: bool, count: int = args.steps):
         g = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             with torch.cuda.graph(g, stream=side):
-                for i in range(args.steps):
+                for i in range(count):
                     step(i, warm)
         torch.cuda.current_stream().wait_stream(side)
-        stabilize_replays.append(_stabilize(g))
         return g
 
     def timed(g):
@@ -1434,16 +1486,33 @@ def main() -> None:
     stabilize_replays = []
 
     st0 = copies[0][0].stats()
-    g_cold = capture(False)
-    first_ms = timed(g_cold)
-    # nine more samples of the same K steps: `value` is the median of the ten
-    # timed regions (hipEvents around >= 200 launches per sample,
-    # median of 10 samples; the upper median for an even count), so one slow
-    # region on a fresh box does not set the line; the first region, min and
-    # max are reported beside it
-    samples = sorted([first_ms] + [timed(g_cold) for _ in range(9)])
+    # more steps than GRAPH_CHUNK: one graph of whole rotations over the
+    # copies, replayed back to back, and one of the remaining steps, so the
+    # timed region still holds exactly `steps` launches in rotation order
+    chunk = max(1, GRAPH_CHUNK // ncopies) * ncopies
+    whole, rest = divmod(args.steps, chunk) if args.steps > chunk else (0, args.steps)
+    side = min(args.steps, chunk)  # launches per graph of the legs timed beside the value (--full)
+    g_chunk = capture(False, chunk) if whole else None
+    g_rest = capture(False, rest) if rest else None
+    stabilize_replays.append(_stabilize(g_chunk or g_rest))
+
+    def replay_cold():
+        for _ in range(whole):
+            g_chunk.replay()
+        if g_rest is not None:
+            g_rest.replay()
+
+    first_ms = _timed_events(replay_cold, world)
+    if args.dump_outputs and rank == 0:  # the last timed step's Y, before any other leg writes it
+        dump_outputs(args.dump_outputs, copies[(args.steps - 1) % ncopies][2])
+    # --full: nine more samples of the same K steps: `value` is then the median
+    # of the ten timed regions (hipEvents around >= 200 launches per
+    # sample, median of 10 samples; the upper median for an even count); the
+    # first region, min and max are reported beside it.  A plain run's value
+    # is its one timed region.
+    samples = sorted([first_ms] + [_timed_events(replay_cold, world) for _ in range(9 if args.full else 0)])
     span_ms = samples[len(samples) // 2]
-    del g_cold
+    del g_chunk, g_rest
     # bind + execute per step with the values changed every step (an
     # iterative caller whose matrix values change between products): each
     # copy alternates between two value arrays, every step re-binds its plan
@@ -1465,8 +1534,8 @@ def main() -> None:
                 rp_, ci_, _ = plan.A.ptrs()
                 _call("smfv_plan_execute", plan._plan, rp_, ci_, vals.data_ptr(), dX.data_ptr(), K, dY.data_ptr(), K,
                       st_)
-        ms_be, how_be = _graph_or_eager(lambda i: rb_step(i, True), args.steps, world)
-        ms_b, _ = _graph_or_eager(lambda i: rb_step(i, False), args.steps, world)
+        ms_be, how_be = _graph_or_eager(lambda i: rb_step(i, True), side, world)
+        ms_b, _ = _graph_or_eager(lambda i: rb_step(i, False), side, world)
         for plan, _, _ in copies:  # back to the values the check uses
             plan.bind_values()
         torch.cuda.synchronize()
@@ -1486,7 +1555,7 @@ def main() -> None:
                                   tiled_kernel=args.tiled_kernel, live_values=True) for pl, _, _ in copies]
             torch.cuda.synchronize()
             if all(lp.stats()["live_values"] for lp in live):
-                ms_lbe, how_l = _graph_or_eager(lambda i: rb_step(i, True, live), args.steps, world)
+                ms_lbe, how_l = _graph_or_eager(lambda i: rb_step(i, True, live), side, world)
                 rebind["live_values"] = {
                     "bind_plus_execute_ms": round(ms_lbe, 6),
                     "GFLOPs_incl_bind": round(2.0 * nnz * K / (ms_lbe * 1e-3) / 1e9, 3),
@@ -1501,35 +1570,41 @@ def main() -> None:
             torch.cuda.synchronize()
     # the warm leg (same copy every launch) after the cold one; --no-warm
     # leaves it out so a profile of this process holds cold launches only
-    span_ms_w = timed(capture(True)) if not args.no_warm else float("nan")
-    stream_gbps = stream_copy_gbps(dev)
-    copy_floor = size_matched_copy(dev, prob_bytes, ncopies, args.steps, world) if not args.no_copy_floor else None
+    span_ms_w = float("nan")
+    if not args.no_warm:
+        g_warm = capture(True, side)
+        stabilize_replays.append(_stabilize(g_warm))
+        span_ms_w = timed(g_warm)
+        del g_warm
+    stream_gbps = stream_copy_gbps(dev) if args.full else None
+    copy_floor = size_matched_copy(dev, prob_bytes, ncopies, side, world) if not args.no_copy_floor else None
     wr_bytes = 8 * m * K
-    mix_floor = (mix_matched_copy(dev, prob_bytes - wr_bytes, wr_bytes, ncopies, args.steps, world)
+    mix_floor = (mix_matched_copy(dev, prob_bytes - wr_bytes, wr_bytes, ncopies, side, world)
                  if not args.no_copy_floor else None)
     vendor = None
     if variant in ("ROWWISE", "SEQUENTIAL") and not args.no_vendor:
-        vendor = vendor_leg(copies, args, timed, 2.0 * nnz * K)
+        vendor = vendor_leg(copies, side, timed, 2.0 * nnz * K)
     ms_per_step = span_ms / args.steps
     kern_ms = ms_per_step  # average launch duration incl. the graph's kernel boundaries
-    kern_ms_w = span_ms_w / args.steps
+    kern_ms_w = span_ms_w / side
     if world > 1:
         t = torch.tensor([ms_per_step, kern_ms, kern_ms_w], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ms_per_step, kern_ms, kern_ms_w = t.tolist()
-        span_ms_w = kern_ms_w * args.steps
+        span_ms_w = kern_ms_w * side
 
     # result check after timing: configs 4 (sampled rows; the full reference
     # result is too large for the host) and the cop20k configs (device compare
-    # against the untiled row kernel, bit for bit)
+    # against the untiled row kernel, bit for bit); --full
     chk = None
     plan, dX, dY = copies[0]
-    plan.run(dX, dY)
-    torch.cuda.synchronize()
-    if rank == 0 and not cop:
+    if args.full:
+        plan.run(dX, dY)
+        torch.cuda.synchronize()
+    if args.full and rank == 0 and not cop:
         rows = sampling.sample_rows(A.rowPtr, K)
         chk = sampled_check(A, rows, dX, dY, exact=variant != "NONZERO")
-    elif rank == 0:
+    elif args.full and rank == 0:
         ref = smfv.SpmmPlan(smfv.Variant.SEQUENTIAL, plan.A, K, tiles="off")
         Yr = torch.empty_like(dY)
         ref.run(dX, Yr)
@@ -1571,14 +1646,15 @@ def main() -> None:
                          "kernel": kname,
                          "algorithmic_bytes_per_launch": prob_bytes,
                          "avg_launch_ms": round(kern_ms, 6),
-                         "timing": "HIP events around one hipGraph replay of all timed launches; "
-                                   "median of 10 such timed regions",
+                         "timing": "HIP events around the hipGraph replay of all timed launches (one graph up to "
+                                   f"{GRAPH_CHUNK} launches, else that graph replayed back to back); "
+                                   + ("median of 10 such timed regions" if args.full else "one timed region"),
                          "untimed_replays_before_timing": stabilize_replays,
                          "samples_ms_per_step": {"n": len(samples), "median": round(samples[len(samples) // 2] / args.steps, 6),
                                                  "first_region": round(first_ms / args.steps, 6),
                                                  "min": round(samples[0] / args.steps, 6),
                                                  "max": round(samples[-1] / args.steps, 6)},
-                         "stream_copy_GBps": round(stream_gbps, 1),
+                         "stream_copy_GBps": round(stream_gbps, 1) if stream_gbps else None,
                          "frac_of_stream_copy": round(achieved / stream_gbps, 4) if stream_gbps else None,
                          "size_matched_copy": (dict(copy_floor, frac_of_copy_time=round(copy_floor["avg_launch_ms"] / kern_ms, 4))
                                                if copy_floor else None),
@@ -1590,7 +1666,7 @@ def main() -> None:
                      "live_values": st["live_values"], "paired_rows": st.get("paired_rows"),
                      "est_reuse_sampled": round(st["est_reuse"], 3), "direct_rows": st["direct_rows"],
                      "create_s": round(t_plan[0], 3), "analysis_ms": round(st["analysis_ms"], 1),
-                     "bind_ms": round(bind_ms, 4), "snapshot_entries": st["snapshot_entries"],
+                     "bind_ms": round(bind_ms, 4) if bind_ms is not None else None, "snapshot_entries": st["snapshot_entries"],
                      "rebind_each_step": rebind,
                      "xcd_parts": st["xcd_parts"], "footprint_8_ranges": round(st["footprint"], 3),
                      "note": "create = host analysis + upload, once per pattern; bind = values snapshot "
@@ -1601,13 +1677,16 @@ def main() -> None:
                              if kind == "pow10m" else None),
             "warm": ({"note": "same copy every launch (working set in the 256 MiB Infinity Cache)",
                       "avg_launch_ms": round(kern_ms_w, 6), "achieved_GBps": round(achieved_w, 1),
-                      "GFLOPs": round(world * flops / (span_ms_w / args.steps * 1e-3) / 1e9, 3)}
+                      "GFLOPs": round(world * flops / (span_ms_w / side * 1e-3) / 1e9, 3)}
                      if not args.no_warm else None),
             "effective_GFLOPs_per_gpu": round(flops / (ms_per_step * 1e-3) / 1e9, 3),
             "check": chk,
             "cpu_baseline": cpu,
             "vendor_rocsparse": vendor,
+            "full": args.full,
         }
+        if args.dump_outputs:
+            out["dumped_outputs"] = os.path.join(args.dump_outputs, "Y.npy")
         if fallback is not None:
             out["decomposed_fallback"] = {"reason": fallback,
                                           "note": "the decomposed (RCCL) mode could not start; these are replicas"}

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/ab_geom_k
 for cfg in ${CFGS:-cop20k_k128 cop20k_k32}; do
  for r in 1 2 3; do
   for g in ws1 ws3; do
-    timeout -k 10 200 python bench.py --config $cfg --tiled-kernel $g --no-cpu-baseline --no-vendor --no-copy-floor --no-rebind ${EXTRA:-} \
+    timeout -k 10 200 python bench.py --full --config $cfg --tiled-kernel $g --no-cpu-baseline --no-vendor --no-copy-floor --no-rebind ${EXTRA:-} \
       > gpurun_out/ab_geom_k/${cfg}_${g}_$r.json 2> gpurun_out/ab_geom_k/${cfg}_${g}_$r.log || exit $?
     tail -n 1 gpurun_out/ab_geom_k/${cfg}_${g}_$r.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$cfg $g', round(d['ms_per_step']*1e3, 3), d['roofline']['frac'], d['check']['ok'], d['check']['max_abs_diff'])"
   done

@@ -10,7 +10,7 @@ mkdir -p gpurun_out/ab
 for cfg in ${CFGS:-cop20k_k32 cop20k_k128 cop20kirr_k32}; do
  for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS:-libsmfv.so libsmfv_ab.so}; do
-    SMFV_LIB=$lib timeout -k 10 200 python bench.py --config $cfg --no-cpu-baseline --no-vendor --no-copy-floor \
+    SMFV_LIB=$lib timeout -k 10 200 python bench.py --full --config $cfg --no-cpu-baseline --no-vendor --no-copy-floor \
         --no-rebind ${EXTRA:-} > gpurun_out/ab/ab_${cfg}_${lib%.so}_$r.json 2> gpurun_out/ab/ab_${cfg}_${lib%.so}_$r.log || exit $?
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('$cfg', '$lib', round(d['ms_per_step']*1e3, 3), d['roofline']['frac'], d['check']['ok'], d['check'].get('max_abs_diff'))" gpurun_out/ab/ab_${cfg}_${lib%.so}_$r.json
   done

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out; mkdir -p "$OUT"
 TAG=${TAG:-abargs}
 IFS=';' read -ra SETS <<< "${AB_LIST:?set AB_LIST}"
 for a in "${SETS[@]}"; do
-  timeout -k 10 ${BENCH_TIMEOUT:-240} python bench.py --no-cpu-baseline --no-vendor $a \
+  timeout -k 10 ${BENCH_TIMEOUT:-240} python bench.py --full --no-cpu-baseline --no-vendor $a \
       > "$OUT/ab_tmp.json" 2>> "$OUT/ab_$TAG.log"
   rc=$?
   if [ $rc -ne 0 ]; then echo "rc=$rc for: $a"; tail -5 "$OUT/ab_$TAG.log"; exit $rc; fi

@@ -10,7 +10,7 @@ TAG=${TAG:-list}
 IFS=';' read -ra SETS <<< "${BENCH_LIST:?set BENCH_LIST}"
 for a in "${SETS[@]}"; do
   echo "== $a" | tee -a "$OUT/benchlist_$TAG.log"
-  timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py $a > "$OUT/benchlist_tmp.json" 2>> "$OUT/benchlist_$TAG.log"
+  timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py --full $a > "$OUT/benchlist_tmp.json" 2>> "$OUT/benchlist_$TAG.log"
   rc=$?
   if [ $rc -ne 0 ]; then echo "rc=$rc for: $a"; tail -5 "$OUT/benchlist_$TAG.log"; exit $rc; fi
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); d['_args']=sys.argv[2]; print(json.dumps(d))" "$OUT/benchlist_tmp.json" "$a" >> "$OUT/benchlist_$TAG.jsonl"

@@ -17,13 +17,13 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   rc=$?; echo "smoke rc=$rc"; tail -n 5 "$OUT/smoke_$TAG.log"
   ok $rc || exit $rc
 fi
-timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py ${BENCH_ARGS:-} > "$OUT/bench_$TAG.log" 2>&1
+timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_$TAG.log" 2>&1
 rc=$?; echo "bench rc=$rc"; tail -c 4000 "$OUT/bench_$TAG.log"
 [ $rc -eq 0 ] || exit $rc
 if [ "${SKIP_PROF:-0}" != 1 ]; then
   export TMPDIR=/tmp
   (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o prof --output-format csv \
-      -- python3 "$ROOT/bench.py" --no-cpu-baseline --steps 100 --warmup 10 ${BENCH_ARGS:-} > "$OUT/prof_$TAG.log" 2>&1)
+      -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 100 --warmup 10 ${BENCH_ARGS:-} > "$OUT/prof_$TAG.log" 2>&1)
   rc=$?; echo "rocprof rc=$rc"
   find "$OUT/prof_$TAG" -name "*kernel_stats.csv" -exec head -n 12 {} \;
 fi

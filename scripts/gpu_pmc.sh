@@ -15,7 +15,7 @@ IFS=';' read -r -a GROUPS_ARR <<< "$SETS"
 for ctrs in "${GROUPS_ARR[@]}"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctrs -d "$OUT/pmc_$TAG/p$i" -o pmc --output-format csv \
-     -- python3 "$ROOT/bench.py" --no-cpu-baseline --steps 20 --warmup 2 ${PMC_ARGS:-} > "$OUT/pmc_$TAG/p$i.log" 2>&1
+     -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 20 --warmup 2 ${PMC_ARGS:-} > "$OUT/pmc_$TAG/p$i.log" 2>&1
   rc=$?; echo "pmc pass $i ($ctrs) rc=$rc"
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 done

@@ -77,9 +77,10 @@ def test_gpus_n_starts_n_ranks_itself(n):
     N ranks as children (torch.distributed.run) instead of timing one GPU;
     --dry-run has them meet over gloo without touching a GPU.  stdout is ONE
     JSON line (rank 0's, re-printed by the parent).  (r6) N = 8 rehearses the
-    driver's scaling run's control plane."""
+    driver's scaling run's control plane.  --full: the line carries the CPU
+    baseline."""
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=240, env=_env_without_world(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -98,6 +99,35 @@ def test_gpus_n_starts_n_ranks_itself(n):
         assert cpu["kind"] == "reference"
         assert cpu["cores"] == min(16 * n, len(os.sched_getaffinity(0)))
         assert f"{n}-GPU line" in cpu["note_n_gpus"]
+
+
+def test_plain_dry_run_times_no_cpu_baseline():
+    """Without --full the bench measures nothing beside its headline figure:
+    the dry run's line carries no CPU baseline (and mpiexec never starts)."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"],
+                       capture_output=True, text=True, timeout=120, env=_env_without_world(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["dry_run"] and line["n_gpus"] == 1 and line["cpu_baseline"] is None
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs writes Y.npy in float64: the whole array when it fits
+    the 64 MB limit, else the same ascending row sample on every call."""
+    import numpy as np
+    import torch
+    Y = torch.arange(1000 * 32, dtype=torch.float64).reshape(1000, 32)
+    bench.dump_outputs(str(tmp_path / "a"), Y)
+    got = np.load(tmp_path / "a" / "Y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, Y.numpy())
+    big = torch.arange(300_000, dtype=torch.float64)[:, None].expand(300_000, 32)  # 76.8 MB as float64
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    b, c = np.load(tmp_path / "b" / "Y.npy"), np.load(tmp_path / "c" / "Y.npy")
+    assert os.path.getsize(tmp_path / "b" / "Y.npy") <= 64_000_000 and b.dtype == np.float64
+    assert b.shape[1] == 32 and 200_000 < b.shape[0] < 300_000
+    assert np.all(np.diff(b[:, 0]) > 0) and np.array_equal(b, c)  # distinct rows, ascending, the same both times
 
 
 def test_gpus_must_match_world_size():
