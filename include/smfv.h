@@ -161,7 +161,10 @@ typedef struct smfv_plan_s *smfv_plan_t;
 /* Opt-in (BASELINE config 3's "MFMA K-panel", kept as a measured
  * alternative): the tiles run as dense 16 x 4 blocks of A on
  * v_mfma_f64_16x16x4f64 (k_rows_mfma).  Sums are reassociated by the MFMA:
- * within tolerance, not bit-identical. */
+ * within tolerance, not bit-identical.  The MFMA plan requires a finite X:
+ * the dense blocks' zeros multiply every staged X row, so an inf or NaN in X
+ * row c turns the rows of any 16-row group that uses c into NaN, also those
+ * that do not reference c (every other plan keeps them finite). */
 #define SMFV_PLAN_MFMA 16
 /* Opt-in (measured slower, kept for A/B): the tiled plan cuts the first
  * tile of each of the kernel's blocks in two and runs the halves first and

@@ -133,7 +133,10 @@ class SpmmPlan:
     sequence (capturable into a hipGraph).
 
     tiles: "auto" (stage when re-use >= 3), "off", or "force".  fma: opt-in
-    fused multiply-add in the tiled kernel (SMFV_PLAN_FMA).  rows=(begin,
+    fused multiply-add in the tiled kernel (SMFV_PLAN_FMA).  mfma: opt-in
+    dense-block MFMA tiles (SMFV_PLAN_MFMA); the MFMA plan requires a finite
+    X, because the dense blocks' zeros multiply every staged X row (an inf or
+    NaN in X reaches rows that do not reference it).  rows=(begin,
     end): plan of that row block only (smfv_plan_create_rows; run() writes
     the block's rows to Y[0:end-begin]).  xcd_parts: "auto" (one row range
     per XCD when their X footprints allow it) or "one" (one wavefront cut in
