@@ -228,6 +228,13 @@ typedef struct smfv_plan_s *smfv_plan_t;
  * forces one row per team, ROW_PAIRS forces pairs (A/B, tests). */
 #define SMFV_PLAN_SINGLE_ROWS 16384
 #define SMFV_PLAN_ROW_PAIRS 32768
+/* The plan will be executed with smfv_plan_execute_axpby (below), which
+ * returns SMFV_ERR_INVALID for a plan without this flag; smfv_plan_execute is
+ * unaffected by it.  Create chooses the form of the epilogue
+ * (smfv_plan_epilogue_mode).  AXPBY_TWO_PASS forces the two-pass form (A/B
+ * runs and tests) and implies AXPBY. */
+#define SMFV_PLAN_AXPBY 65536
+#define SMFV_PLAN_AXPBY_TWO_PASS 131072
 SMFV_API int smfv_plan_create(smfv_plan_t *plan, int variant, int m, int n, int64_t nnz,
                               const int *h_row_ptr, const int *h_col_idx, int K, int flags);
 /* Plan of the row block [row_begin, row_end) of a CSR matrix (h_row_ptr /
@@ -283,6 +290,51 @@ SMFV_API int smfv_spmv_chunks_analyse(int row_begin, int row_end, int n, const i
 SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx,
                                const double *d_values, const double *d_X, int64_t ldx,
                                double *d_Y, int64_t ldy, void *stream);
+/* Y <- alpha * A * X + beta * Y, in place, for a plan created with
+ * SMFV_PLAN_AXPBY: the inner step of block CG, LOBPCG, Chebyshev filtering
+ * and subspace iteration.  Same argument rules, values contract (bind),
+ * stream ordering and error reporting as smfv_plan_execute; asynchronous on
+ * the stream and graph-capturable, no allocation and no synchronisation.
+ *
+ * With s the row sum exactly as smfv_plan_execute computes it and y0 the
+ * value in Y before the call:
+ *   beta != 0:  y = fl(fl(alpha * s) + fl(beta * y0)) -- two multiplies and
+ *               one add, each rounded, never contracted into an FMA
+ *               (SMFV_PLAN_FMA plans included);
+ *   beta == 0:  y = fl(alpha * s).  Y is NOT read: a NaN or inf in y0 does not
+ *               propagate, and nothing is added, so the sign of a zero sum
+ *               survives.  Hence alpha = 1, beta = 0 gives the bits of
+ *               smfv_plan_execute.
+ * alpha is always applied by multiplication (no shortcut for alpha == 0:
+ * 0 * inf is NaN, as in IEEE).  The operation covers the plan's rows and the
+ * K columns only; padding beyond K (ldy > K) is neither read nor written.
+ * SEQUENTIAL / ROWWISE / COLUMNWISE: bit-identical to the formula applied to
+ * the reference's sequential sums, NaN for NaN and the sign of zero
+ * included.  NONZERO: |Y - Yexp| <= 1e-12 * (|alpha| * sum|a||x| + |beta| *
+ * |y0|) elementwise.
+ *
+ * Two forms, chosen at create (smfv_plan_epilogue_mode):
+ *   1 fused     the epilogue runs in the store of the kernel that computed
+ *               the sum (k_rows_ws, k_rows_list, k_rows_mh, k_rows, every
+ *               run-time fallback of execute included): one launch, y0 read
+ *               once by the lane that overwrites it, no read at beta == 0.
+ *               SEQUENTIAL / ROWWISE / COLUMNWISE plans with K >= 2 that are
+ *               not SMFV_PLAN_FMA, SMFV_PLAN_MFMA or k_rows_wsn plans.
+ *   2 two-pass  everything else (K = 1, every NONZERO plan -- its kernels
+ *               store partial sums --, FMA, MFMA, k_rows_wsn) and any plan
+ *               with SMFV_PLAN_AXPBY_TWO_PASS: the plan's own launches into a
+ *               plan-owned scratch of m x K doubles (allocated at create,
+ *               counted in the plan's device bytes), then one k_axpby pass.
+ * Out of scope: distributed plans (the flag passes through to the rank-local
+ * plan harmlessly; no smfv_dist_plan_* axpby execute exists), the plan-less
+ * smfv_spmm_csr_f64 family, the C++ drop-in and the CLI (the reference has no
+ * such call), and bench.py. */
+SMFV_API int smfv_plan_execute_axpby(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx,
+                                     const double *d_values, const double *d_X, int64_t ldx,
+                                     double alpha, double beta, double *d_Y, int64_t ldy, void *stream);
+/* *mode = 0 (no epilogue: the plan lacks SMFV_PLAN_AXPBY), 1 (fused) or 2
+ * (two-pass). */
+SMFV_API int smfv_plan_epilogue_mode(smfv_plan_t plan, int *mode);
 /* out[0] tiled (0/1), [1] tiles, [2] staged X rows per panel, [3] re-use
  * (tiled non-zeros / staged rows), [4] plan device bytes, [5] direct rows,
  * [6] first row of the block, [7] re-use estimated on the sample tiles (-1:

@@ -63,6 +63,9 @@ _SIGS = {
     "smfv_plan_bind_values": (c_int, [c_void_p, c_void_p, c_void_p]),
     "smfv_plan_execute": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                   c_void_p, c_int64, c_void_p]),
+    "smfv_plan_execute_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_double, c_double, c_void_p, c_int64, c_void_p]),
+    "smfv_plan_epilogue_mode": (c_int, [c_void_p, _PI]),
     "smfv_plan_stats": (c_int, [c_void_p, _PD]),
     "smfv_plan_destroy": (c_int, [c_void_p]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -15,6 +15,10 @@
 //   k_combine_blocks     <- SC/...NonZeroElement.cpp:88 (MPI_Reduce SUM)
 //   k_compare            <- SC/utils.cpp:38-63 (areMatricesEqual)
 //   k_copy16             bench probe: measured HBM streaming rate
+//   k_ws_axpby(_live), k_rows_list_axpby, k_rows_mh / k_rows <.., Axpby>, k_axpby
+//            Y = alpha A X + beta Y (smfv_plan_execute_axpby): the row kernels
+//            above with the epilogue in their stores, and the second pass of
+//            the plans that cannot fuse it; no counterpart in the reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -40,6 +44,7 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -97,6 +102,47 @@ template <> struct VecT<2> {
         return make_double2(acc.x + px, acc.y + py);
     }
 };
+
+// ---------------------------------------------------------------------------
+// The alpha / beta epilogue of smfv_plan_execute_axpby (include/smfv.h): with
+// s the row sum, y = fl(fl(alpha * s) + fl(beta * y0)), or fl(alpha * s) when
+// beta == 0 (Y is then not read).  Two multiplies and an add, each rounded:
+// fp contraction is off for this file, FMA plans included.  alpha and beta
+// are kernel arguments (SGPRs), so the beta test is one scalar branch per
+// store site, not a per-lane select behind a load.  y0 is read once, by the
+// lane that overwrites it, at the store: the row's read-ahead registers are
+// dead there.  It is a non-temporal load, like every other read-once stream
+// of this file: against a plain load the fused step measured 28.6-28.9
+// against 30.1-30.5 us on the cop20k stand-in, K = 32, and the two-pass step
+// 40.6-40.8 against 42.4-42.7 us (profiles/axpby/README.md).
+// ---------------------------------------------------------------------------
+struct Axpby {
+    double alpha, beta;
+};
+typedef double axpby_d2 __attribute__((ext_vector_type(2)));
+template <class T> __device__ __forceinline__ T axpby_y0(const T *y)
+{
+    return __builtin_nontemporal_load(y);
+}
+__device__ __forceinline__ double axpby_one(Axpby e, double s, const double *y)
+{
+    const double as = e.alpha * s;
+    if (e.beta == 0.0) return as;  // launch-uniform
+    const double by = e.beta * axpby_y0(y);
+    return as + by;
+}
+template <int VEC> __device__ __forceinline__ typename VecT<VEC>::T axpby_vec(Axpby e, typename VecT<VEC>::T s, const double *y)
+{
+    if constexpr (VEC == 1) {
+        return axpby_one(e, s, y);
+    } else {
+        const double ax = e.alpha * s.x, ay = e.alpha * s.y;
+        if (e.beta == 0.0) return make_double2(ax, ay);  // launch-uniform
+        const axpby_d2 y0 = axpby_y0(reinterpret_cast<const axpby_d2 *>(y));
+        const double bx = e.beta * y0.x, by = e.beta * y0.y;
+        return make_double2(ax + bx, ay + by);
+    }
+}
 
 // Accumulate nnz [js, je) of one row into acc (team-uniform control flow).
 // X is indexed at column offset c (this lane's VEC columns); cok = lane owns
@@ -174,13 +220,18 @@ row_segment(int js, int je, const int *__restrict__ ci, const double *__restrict
 // k_rows: rows [row_begin, row_begin + nrows) of Y (written at Y + lrow*ldy),
 // columns [0, K) of the (possibly offset) X.
 // ---------------------------------------------------------------------------
-template <int TEAM, int VEC>
+// EP: empty (Y = A X; the kernel as it was before the epilogue existed) or
+// one Axpby kernel argument, applied in the store (smfv_plan_execute_axpby).
+// The body stays in the kernel: moved into a shared device function, the
+// plain instances compiled to different code.
+template <int TEAM, int VEC, class... EP>
 __global__ __launch_bounds__(256) void k_rows(int row_begin, int nrows, const int *__restrict__ rp,
                                               const int *__restrict__ ci,
                                               const double *__restrict__ va,
                                               const double *__restrict__ X, int64_t ldx, int K,
-                                              double *__restrict__ Y, int64_t ldy)
+                                              double *__restrict__ Y, int64_t ldy, EP... ep)
 {
+    static_assert(sizeof...(EP) <= 1, "at most one epilogue");
     using V = VecT<VEC>;
     constexpr int RPB = 256 / TEAM;  // rows per block
     const int blk = xcd_remap(blockIdx.x, gridDim.x);
@@ -195,7 +246,11 @@ __global__ __launch_bounds__(256) void k_rows(int row_begin, int nrows, const in
         const int c = p * TEAM * VEC + tl * VEC;
         const bool cok = c < K;
         typename V::T acc = row_segment<TEAM, VEC>(js, je, ci, va, X, ldx, c, cok, V::zero());
-        if (cok) V::store(yrow + c, acc);
+        if constexpr (sizeof...(EP) == 1) {
+            if (cok) V::store(yrow + c, axpby_vec<VEC>(ep..., acc, yrow + c));
+        } else {
+            if (cok) V::store(yrow + c, acc);
+        }
     }
 }
 
@@ -373,15 +428,17 @@ __global__ __launch_bounds__(NT) void k_spmv_chunks(const int4 *__restrict__ hdr
 constexpr int stage_cap(int team) { return team <= 1 ? 4096 : team == 2 ? 3072 : team == 4 ? 1536 : 1024; }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <int TEAM, int H, int U, bool BUF>
+// EP: empty (Y = A X) or one Axpby kernel argument applied in the store, as in k_rows
+template <int TEAM, int H, int U, bool BUF, class... EP>
 __global__ __launch_bounds__(256) void k_rows_mh(int row_begin, int nrows,
                                                  const int *__restrict__ rp,
                                                  const int *__restrict__ ci,
                                                  const double *__restrict__ va,
                                                  const double *__restrict__ X, int64_t ldx,
                                                  uint32_t xbytes, int K, double *__restrict__ Y,
-                                                 int64_t ldy)
+                                                 int64_t ldy, EP... ep)
 {
+    static_assert(sizeof...(EP) <= 1, "at most one epilogue");
     constexpr int RPB = 256 / TEAM;
     constexpr int CP = 2 * TEAM * H;  // columns per pass
     constexpr int STAGE_CAP = stage_cap(TEAM);
@@ -476,7 +533,13 @@ __global__ __launch_bounds__(256) void k_rows_mh(int row_begin, int nrows,
         if (live)
 #pragma unroll
             for (int h = 0; h < H; ++h)
-                if (ok[h]) *reinterpret_cast<double2 *>(yrow + cb + 2 * TEAM * h) = acc[h];
+                if (ok[h]) {
+                    if constexpr (sizeof...(EP) == 1)
+                        *reinterpret_cast<double2 *>(yrow + cb + 2 * TEAM * h) =
+                            axpby_vec<2>(ep..., acc[h], yrow + cb + 2 * TEAM * h);
+                    else
+                        *reinterpret_cast<double2 *>(yrow + cb + 2 * TEAM * h) = acc[h];
+                }
     }
 }
 
@@ -607,12 +670,13 @@ struct WsXcd {
 // vidx[t * vstride + slot] of each slot (WsPlan::live): no snapshot, no bind
 // The body is shared by the two kernels below: k_rows_ws (the snapshot,
 // with the r4 argument list) and k_rows_ws_live (r5, three more arguments).
-template <int CW, int LW, int PPW, int UCAP, int NCAP, bool FMA, bool SADDR, bool NARROW, bool LIVE>
+// (AX: the alpha / beta epilogue in the store, k_ws_axpby / k_ws_axpby_live)
+template <int CW, int LW, int PPW, int UCAP, int NCAP, bool FMA, bool SADDR, bool NARROW, bool LIVE, bool AX = false>
 __device__ __forceinline__ void ws_body(int xfirst, int xend, int npanel, int chunked, const int *__restrict__ grec,
                                         const int *__restrict__ lrec, const uint8_t *__restrict__ loff,
                                         const double *__restrict__ tv, const double *__restrict__ X, int64_t ldx,
                                         double *__restrict__ Y, int64_t ldy, const int *__restrict__ vidx,
-                                        int vstride, unsigned tv_bytes)
+                                        int vstride, unsigned tv_bytes, Axpby ep = Axpby{})
 {
     using namespace ws;
     using L = Lay<CW, LW, PPW, UCAP, NCAP>;
@@ -836,6 +900,24 @@ __device__ __forceinline__ void ws_body(int xfirst, int xend, int npanel, int ch
             // DMA issue, measured 25.6 -> 28.1 us)
             auto store = [&](int r, d2 s0, d2 s1) {
                 double *y = Y + (int64_t)r * ldy + p * TILE_KP + 2 * tl;
+                if constexpr (AX) {
+                    // y0 is loaded here, after the row's last sum: the X /
+                    // value / offset read-ahead registers are dead, so its 4
+                    // doubles do not raise the kernel's peak (beta == 0: one
+                    // scalar branch, no load)
+                    s0 = ep.alpha * s0;
+                    if constexpr (!NARROW) s1 = ep.alpha * s1;
+                    if (ep.beta != 0.0) {
+                        if constexpr (NARROW) {
+                            if (2 * tl < kwin) s0 = s0 + ep.beta * axpby_y0(reinterpret_cast<const d2 *>(y));
+                        } else {
+                            const d2 y0 = axpby_y0(reinterpret_cast<const d2 *>(y + 16 * par));
+                            const d2 y1 = axpby_y0(reinterpret_cast<const d2 *>(y + 16 * (par ^ 1)));
+                            s0 = s0 + ep.beta * y0;
+                            s1 = s1 + ep.beta * y1;
+                        }
+                    }
+                }
                 if constexpr (NARROW) {
                     if (2 * tl < kwin)  // columns 2 tl, 2 tl + 1 of the window (from either image half)
                         __builtin_nontemporal_store(s0, reinterpret_cast<d2 *>(y));
@@ -982,6 +1064,42 @@ __global__ __launch_bounds__(64 * (CW + LW), CW == 4 ? 4 : 1) void k_rows_ws_liv
                                                              loff, tv, X, ldx, Y, ldy, vidx, vstride, tv_bytes);
 }
 
+// The epilogue forms (smfv_plan_execute_axpby): the same bodies with AX, alpha
+// and beta as two more arguments.  Their names do not contain "k_rows_ws" on
+// purpose: the register-budget test of the plain instances parses that name;
+// tests/test_axpby_host.py holds these to the same budgets.  No FMA form: an
+// SMFV_PLAN_FMA plan takes the two-pass epilogue.
+template <int CW, int LW, int PPW, int UCAP, int NCAP, bool SADDR = true, bool NARROW = false>
+__global__ __launch_bounds__(64 * (CW + LW), CW == 4 ? 4 : 1) void k_ws_axpby(WsXcd xr, int npanel, int chunked,
+                                                     const int *__restrict__ grec,
+                                                     const int *__restrict__ lrec,
+                                                     const uint8_t *__restrict__ loff,
+                                                     const double *__restrict__ tv,
+                                                     const double *__restrict__ X, int64_t ldx,
+                                                     double *__restrict__ Y, int64_t ldy, double alpha, double beta)
+{
+    const int x = blockIdx.x & 7;
+    ws_body<CW, LW, PPW, UCAP, NCAP, false, SADDR, NARROW, false, true>(xr.first[x], xr.first[x + 1], npanel, chunked,
+                                                                       grec, lrec, loff, tv, X, ldx, Y, ldy, nullptr, 0,
+                                                                       0u, Axpby{alpha, beta});
+}
+template <int CW, int LW, int PPW, int UCAP, int NCAP, bool NARROW = false>
+__global__ __launch_bounds__(64 * (CW + LW), CW == 4 ? 4 : 1) void k_ws_axpby_live(WsXcd xr, int npanel, int chunked,
+                                                     const int *__restrict__ grec,
+                                                     const int *__restrict__ lrec,
+                                                     const uint8_t *__restrict__ loff,
+                                                     const double *__restrict__ tv,
+                                                     const double *__restrict__ X, int64_t ldx,
+                                                     double *__restrict__ Y, int64_t ldy,
+                                                     const int *__restrict__ vidx, int vstride, unsigned tv_bytes,
+                                                     double alpha, double beta)
+{
+    const int x = blockIdx.x & 7;
+    ws_body<CW, LW, PPW, UCAP, NCAP, false, true, NARROW, true, true>(xr.first[x], xr.first[x + 1], npanel, chunked,
+                                                                     grec, lrec, loff, tv, X, ldx, Y, ldy, vidx,
+                                                                     vstride, tv_bytes, Axpby{alpha, beta});
+}
+
 // the product instances of k_rows_ws: geometry (smfv_plan.h WsGeom) x FMA x SADDR x NARROW
 #define SMFV_WS_INST(G_) k_rows_ws<G_.cw, G_.lw, G_.ppw, G_.ucap, G_.ncap, FMA, SADDR, NARROW>
 template <bool FMA, bool SADDR, bool NARROW> constexpr auto WS1 = SMFV_WS_INST(WS_GEOM1);
@@ -1009,6 +1127,31 @@ static auto pick_ws_n(int geom, bool fma, bool saddr)
 static auto pick_ws(int geom, bool fma, bool saddr, bool narrow = false)
 {
     return narrow ? pick_ws_n<true>(geom, fma, saddr) : pick_ws_n<false>(geom, fma, saddr);
+}
+// the epilogue instances: geometry x SADDR x NARROW, and live x NARROW
+#define SMFV_WSA_INST(G_) k_ws_axpby<G_.cw, G_.lw, G_.ppw, G_.ucap, G_.ncap, SADDR, NARROW>
+template <bool SADDR, bool NARROW> constexpr auto WSA1 = SMFV_WSA_INST(WS_GEOM1);
+template <bool SADDR, bool NARROW> constexpr auto WSA2 = SMFV_WSA_INST(WS_GEOM2);
+template <bool SADDR, bool NARROW> constexpr auto WSA3 = SMFV_WSA_INST(WS_GEOM3);
+#undef SMFV_WSA_INST
+#define SMFV_WSAL_INST(G_) k_ws_axpby_live<G_.cw, G_.lw, G_.ppw, G_.ucap, G_.ncap, NARROW>
+template <bool NARROW> constexpr auto WSAL1 = SMFV_WSAL_INST(WS_GEOM1);
+template <bool NARROW> constexpr auto WSAL2 = SMFV_WSAL_INST(WS_GEOM2);
+template <bool NARROW> constexpr auto WSAL3 = SMFV_WSAL_INST(WS_GEOM3);
+#undef SMFV_WSAL_INST
+static auto pick_ws_axpby(int geom, bool saddr, bool narrow)
+{
+    if (geom == 2)
+        return narrow ? (saddr ? WSA2<true, true> : WSA2<false, true>) : (saddr ? WSA2<true, false> : WSA2<false, false>);
+    if (geom == 3)
+        return narrow ? (saddr ? WSA3<true, true> : WSA3<false, true>) : (saddr ? WSA3<true, false> : WSA3<false, false>);
+    return narrow ? (saddr ? WSA1<true, true> : WSA1<false, true>) : (saddr ? WSA1<true, false> : WSA1<false, false>);
+}
+static auto pick_ws_axpby_live(int geom, bool narrow)
+{
+    if (geom == 2) return narrow ? WSAL2<true> : WSAL2<false>;
+    if (geom == 3) return narrow ? WSAL3<true> : WSAL3<false>;
+    return narrow ? WSAL1<true> : WSAL1<false>;
 }
 // (r5) the live-values kernel (value pairs DMA'd from the caller's CSR; scalar-base addressing always)
 static auto pick_ws_live(int geom, bool fma, bool narrow)
@@ -1226,12 +1369,13 @@ __global__ __launch_bounds__(1024, 1) void k_rows_wsn(WsXcd xr, const int *__res
 // row, X gathered straight from HBM, CSR order (bit-identical).  `rows` are
 // block-local (Y row), row_begin + row indexes the CSR; the values come from
 // the plan's bound snapshot (tv + doff[team], CSR order), like the tiles'.
-__global__ __launch_bounds__(256) void k_rows_list(int nrows, int kwin, const int *__restrict__ rows,
-                                                   const int64_t *__restrict__ doff, int row_begin,
-                                                   const int *__restrict__ rp, const int *__restrict__ ci,
-                                                   const double *__restrict__ tv,
-                                                   const double *__restrict__ X, int64_t ldx,
-                                                   double *__restrict__ Y, int64_t ldy)
+// (the body is shared by k_rows_list and its epilogue form k_rows_list_axpby)
+template <bool AX>
+__device__ __forceinline__ void rows_list_body(int nrows, int kwin, const int *__restrict__ rows,
+                                               const int64_t *__restrict__ doff, int row_begin,
+                                               const int *__restrict__ rp, const int *__restrict__ ci,
+                                               const double *__restrict__ tv, const double *__restrict__ X,
+                                               int64_t ldx, double *__restrict__ Y, int64_t ldy, Axpby ep)
 {
     const int team = blockIdx.x * 32 + (threadIdx.x >> 3);
     if (team >= nrows) return;
@@ -1245,7 +1389,9 @@ __global__ __launch_bounds__(256) void k_rows_list(int nrows, int kwin, const in
         if (2 * tl >= kwin) return;
         for (int jj = j0; jj < rp[row_begin + row + 1]; ++jj)
             acc0 = VecT<2>::madd(acc0, vrow[jj], *reinterpret_cast<const double2 *>(X + (int64_t)ci[jj] * ldx + 2 * tl));
-        *reinterpret_cast<double2 *>(Y + (int64_t)row * ldy + 2 * tl) = acc0;
+        double *yn = Y + (int64_t)row * ldy + 2 * tl;
+        if constexpr (AX) acc0 = axpby_vec<2>(ep, acc0, yn);
+        *reinterpret_cast<double2 *>(yn) = acc0;
         return;
     }
     for (int jj = j0; jj < rp[row_begin + row + 1]; ++jj) {
@@ -1255,8 +1401,32 @@ __global__ __launch_bounds__(256) void k_rows_list(int nrows, int kwin, const in
         acc1 = VecT<2>::madd(acc1, v, *reinterpret_cast<const double2 *>(px + 16 * (par ^ 1)));
     }
     double *y = Y + (int64_t)row * ldy + cp + 2 * tl;
+    if constexpr (AX) {
+        acc0 = axpby_vec<2>(ep, acc0, y + 16 * par);
+        acc1 = axpby_vec<2>(ep, acc1, y + 16 * (par ^ 1));
+    }
     *reinterpret_cast<double2 *>(y + 16 * par) = acc0;
     *reinterpret_cast<double2 *>(y + 16 * (par ^ 1)) = acc1;
+}
+__global__ __launch_bounds__(256) void k_rows_list(int nrows, int kwin, const int *__restrict__ rows,
+                                                   const int64_t *__restrict__ doff, int row_begin,
+                                                   const int *__restrict__ rp, const int *__restrict__ ci,
+                                                   const double *__restrict__ tv,
+                                                   const double *__restrict__ X, int64_t ldx,
+                                                   double *__restrict__ Y, int64_t ldy)
+{
+    rows_list_body<false>(nrows, kwin, rows, doff, row_begin, rp, ci, tv, X, ldx, Y, ldy, Axpby{});
+}
+// Y = alpha * (A X) + beta * Y in k_rows_list's stores (smfv_plan_execute_axpby)
+__global__ __launch_bounds__(256) void k_rows_list_axpby(int nrows, int kwin, const int *__restrict__ rows,
+                                                         const int64_t *__restrict__ doff, int row_begin,
+                                                         const int *__restrict__ rp, const int *__restrict__ ci,
+                                                         const double *__restrict__ tv,
+                                                         const double *__restrict__ X, int64_t ldx,
+                                                         double *__restrict__ Y, int64_t ldy, double alpha,
+                                                         double beta)
+{
+    rows_list_body<true>(nrows, kwin, rows, doff, row_begin, rp, ci, tv, X, ldx, Y, ldy, Axpby{alpha, beta});
 }
 
 // ---------------------------------------------------------------------------
@@ -1492,6 +1662,28 @@ __global__ __launch_bounds__(256) void k_cut_rows(CutRows cr, const int *__restr
 __global__ __launch_bounds__(256) void k_fill_f64(int64_t n, double v, double *__restrict__ out)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = v;
+}
+
+// k_axpby: the second pass of a two-pass plan (smfv_plan_execute_axpby):
+// Y = alpha * S + beta * Y over m x K, S the plan's scratch (row-major, ld =
+// K) holding the sums the plan's own kernels just wrote.  One lane per VEC
+// doubles (VEC = 2: 16-byte lanes where K, ldy and Y's address allow it).
+// Every byte is touched once: non-temporal both ways.  Padding columns of Y
+// (ldy > K) are neither read nor written; beta == 0 does not read Y.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_axpby(int64_t m, int K, const double *__restrict__ S,
+                                               double *__restrict__ Y, int64_t ldy, double alpha, double beta)
+{
+    using T = std::conditional_t<VEC == 2, axpby_d2, double>;
+    const int kv = K / VEC;  // lanes per row (VEC == 2 only for even K)
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= m * kv) return;
+    const int64_t row = g / kv;
+    const int c = (int)(g - row * kv) * VEC;
+    T *y = reinterpret_cast<T *>(Y + row * ldy + c);
+    T r = alpha * __builtin_nontemporal_load(reinterpret_cast<const T *>(S + row * K + c));
+    if (beta != 0.0) r = r + beta * axpby_y0(y);  // launch-uniform
+    __builtin_nontemporal_store(r, y);
 }
 
 // ---------------------------------------------------------------------------
@@ -1848,7 +2040,7 @@ static RowCfg row_cfg_for(int K)
 
 static int launch_rows_mh(int row_begin, int nrows, const int *rp, const int *ci, const double *va,
                           const double *X, int64_t ldx, int64_t xrows, int K, double *Y,
-                          int64_t ldy, hipStream_t st)
+                          int64_t ldy, hipStream_t st, const Axpby *ep = nullptr)
 {
     const RowCfg cfg = row_cfg_for(K);
     const int rpb = 256 / cfg.team;
@@ -1859,7 +2051,13 @@ static int launch_rows_mh(int row_begin, int nrows, const int *rp, const int *ci
     const uint32_t xbytes = buf ? (uint32_t)xb : 0u;
 #define L(T_, H_, U_)                                                                               \
     if (cfg.team == T_ && cfg.h == H_ && cfg.u == U_) {                                             \
-        if (buf)                                                                                    \
+        if (ep && buf)                                                                              \
+            hipLaunchKernelGGL((k_rows_mh<T_, H_, U_, true, Axpby>), dim3((unsigned)nblk), dim3(256), 0, st,       \
+                               row_begin, nrows, rp, ci, va, X, ldx, xbytes, K, Y, ldy, *ep);       \
+        else if (ep)                                                                                \
+            hipLaunchKernelGGL((k_rows_mh<T_, H_, U_, false, Axpby>), dim3((unsigned)nblk), dim3(256), 0, st,      \
+                               row_begin, nrows, rp, ci, va, X, ldx, xbytes, K, Y, ldy, *ep);       \
+        else if (buf)                                                                               \
             hipLaunchKernelGGL((k_rows_mh<T_, H_, U_, true>), dim3((unsigned)nblk), dim3(256), 0,   \
                                st, row_begin, nrows, rp, ci, va, X, ldx, xbytes, K, Y, ldy);        \
         else                                                                                        \
@@ -1875,13 +2073,17 @@ static int launch_rows_mh(int row_begin, int nrows, const int *rp, const int *ci
 }
 
 static int launch_rows_simple(int row_begin, int nrows, const int *rp, const int *ci, const double *va,
-                              const double *X, int64_t ldx, int K, double *Y, int64_t ldy, hipStream_t st);
+                              const double *X, int64_t ldx, int K, double *Y, int64_t ldy, hipStream_t st,
+                              const Axpby *ep = nullptr);
 
+// ep: the alpha / beta epilogue of a fused plan (the *_axpby instances); NULL
+// launches the plain instances, as before the epilogue existed
 static int launch_rows(int row_begin, int nrows, const int *rp, const int *ci, const double *va,
                        const double *X, int64_t ldx, int64_t xrows, int K, double *Y, int64_t ldy,
-                       hipStream_t st)
+                       hipStream_t st, const Axpby *ep = nullptr)
 {
     if (nrows <= 0 || K <= 0) return SMFV_OK;
+    SMFV_REQUIRE(!(ep && K == 1), "internal: K = 1 has no fused epilogue");
     if (K == 1) {  // SpMV: coalesced CSR stream, products staged in LDS
         // 64 rows / 2,048-entry chunk per 256-lane block: one chunk per block
         // on cop20k (~1,390 non-zeros), 1,894 blocks.  Block-shape sweep on
@@ -1896,14 +2098,15 @@ static int launch_rows(int row_begin, int nrows, const int *rp, const int *ci, c
         return SMFV_OK;
     }
     const int vec = pick_vec(X, ldx, Y, ldy, K);
-    if (vec == 2) return launch_rows_mh(row_begin, nrows, rp, ci, va, X, ldx, xrows, K, Y, ldy, st);
-    return launch_rows_simple(row_begin, nrows, rp, ci, va, X, ldx, K, Y, ldy, st);
+    if (vec == 2) return launch_rows_mh(row_begin, nrows, rp, ci, va, X, ldx, xrows, K, Y, ldy, st, ep);
+    return launch_rows_simple(row_begin, nrows, rp, ci, va, X, ldx, K, Y, ldy, st, ep);
 }
 
 // odd K, unaligned X / Y, or a plan with SMFV_PLAN_SIMPLE_ROWS: one double
 // per lane, the team's (col, val) pairs broadcast by shuffle (k_rows)
 static int launch_rows_simple(int row_begin, int nrows, const int *rp, const int *ci, const double *va,
-                              const double *X, int64_t ldx, int K, double *Y, int64_t ldy, hipStream_t st)
+                              const double *X, int64_t ldx, int K, double *Y, int64_t ldy, hipStream_t st,
+                              const Axpby *ep)
 {
     if (nrows <= 0 || K <= 0) return SMFV_OK;
     const int team = pick_team(K, 1);
@@ -1912,7 +2115,14 @@ static int launch_rows_simple(int row_begin, int nrows, const int *rp, const int
     SMFV_REQUIRE(nblk <= 0x7fffffff, "too many rows for one launch");
 #define L(T_, V_) hipLaunchKernelGGL((k_rows<T_, V_>), dim3((unsigned)nblk), dim3(256), 0, st, \
                                      row_begin, nrows, rp, ci, va, X, ldx, K, Y, ldy)
-    SMFV_TEAM_SWITCH(team, 1, L)
+#define LA(T_, V_) hipLaunchKernelGGL((k_rows<T_, V_, Axpby>), dim3((unsigned)nblk), dim3(256), 0, st, \
+                                      row_begin, nrows, rp, ci, va, X, ldx, K, Y, ldy, *ep)
+    if (ep) {
+        SMFV_TEAM_SWITCH(team, 1, LA)
+    } else {
+        SMFV_TEAM_SWITCH(team, 1, L)
+    }
+#undef LA
 #undef L
     SMFV_LAUNCHED();
     return SMFV_OK;
@@ -2204,6 +2414,11 @@ struct smfv_plan_s {
     uint8_t *cs_aux = nullptr;
     void *ws = nullptr;
     size_t ws_bytes = 0, dev_bytes = 0;
+    // smfv_plan_execute_axpby: 0 no epilogue (plan without SMFV_PLAN_AXPBY), 1
+    // fused into the row kernels' stores, 2 two-pass (the plan's kernels into
+    // ax_scratch, m x K, then k_axpby); chosen at create
+    int epilogue = 0;
+    double *ax_scratch = nullptr;
     hipEvent_t bind_ev = nullptr;          // recorded after the snapshot gather
     hipStream_t bind_stream = nullptr;
     // (r4) NONZERO over an nnz range that cuts rows (a rank's share): the
@@ -2218,7 +2433,7 @@ struct smfv_plan_s {
         delete sub;
         for (void *q : {(void *)tsrc, (void *)bind_items, (void *)tvals, (void *)ws_vidx, (void *)wsn_grec, (void *)wsn_lrec,
                         (void *)wsn_loff, (void *)ws_grec, (void *)ws_lrec, (void *)direct_rows,
-                        (void *)direct_off, (void *)ws_loff, ws, (void *)mf_rec, (void *)mf_ucols, (void *)mf_bstep,
+                        (void *)direct_off, (void *)ws_loff, ws, (void *)ax_scratch, (void *)mf_rec, (void *)mf_ucols, (void *)mf_bstep,
                         (void *)k1_hdr, (void *)k1_rs, (void *)k1_off, (void *)k1_col, (void *)cs_bs,
                         (void *)cs_trow, (void *)cs_tlast, (void *)cs_crec, (void *)cs_aux})
             if (q) (void)hipFree(q);
@@ -2593,7 +2808,8 @@ int smfv::plan_create(smfv_plan_t *out, int variant, int row_begin, int m, int n
         const int fi = h_rp[f] < nnz_base ? f + 1 : f, li = h_rp[l + 1] > nnz_end ? l - 1 : l;
         if (li >= fi) {
             smfv_plan_t sub = nullptr;
-            if (plan_create(&sub, SMFV_ROWWISE, fi, li - fi + 1, n, h_rp[fi], h_rp[li + 1], h_rp, h_ci, K, flags, -1) ==
+            if (plan_create(&sub, SMFV_ROWWISE, fi, li - fi + 1, n, h_rp[fi], h_rp[li + 1], h_rp, h_ci, K,
+                            flags & ~(SMFV_PLAN_AXPBY | SMFV_PLAN_AXPBY_TWO_PASS), -1) ==
                     SMFV_OK &&
                 sub->tiled) {
                 p->sub = sub;
@@ -2611,6 +2827,21 @@ int smfv::plan_create(smfv_plan_t *out, int variant, int row_begin, int m, int n
             } else {
                 delete sub;  // no gain: the merge path keeps the whole range
             }
+        }
+    }
+    if (!rc && (flags & (SMFV_PLAN_AXPBY | SMFV_PLAN_AXPBY_TWO_PASS))) {
+        // The epilogue's form.  Fused: the plans whose every branch ends in
+        // k_rows_ws / k_rows_list / k_rows_mh / k_rows, which all carry the
+        // epilogue (the run-time fallbacks of execute included).  Two-pass:
+        // K = 1, NONZERO (its kernels store partial sums), FMA, MFMA and
+        // k_rows_wsn plans, and any plan that asks for it.
+        const bool fused = !(flags & (SMFV_PLAN_AXPBY_TWO_PASS | SMFV_PLAN_FMA | SMFV_PLAN_MFMA)) &&
+                           variant != SMFV_NONZERO && K >= 2 && !p->wsn && !p->mfma && !p->k1;
+        p->epilogue = fused ? 1 : 2;
+        if (!fused && m > 0 && K > 0) {
+            const size_t b = (size_t)m * (size_t)K * sizeof(double);
+            fail_hip(hipMalloc(reinterpret_cast<void **>(&p->ax_scratch), b), "hipMalloc(axpby scratch)");
+            if (!rc) p->dev_bytes += b;
         }
     }
     if (rc) {
@@ -2897,6 +3128,7 @@ SMFV_API int smfv_plan_stats(smfv_plan_t plan, double out[SMFV_PLAN_STATS])
         smfv_plan_stats(plan->sub, out);
         out[6] = plan->row_begin;
         out[8] = plan->analysis_ms;
+        if (plan->ax_scratch) out[4] += (double)plan->m * plan->K * sizeof(double);  // the two-pass scratch is the range's own
         return SMFV_OK;
     }
     out[0] = plan->tiled ? 1.0 : 0.0;
@@ -2920,9 +3152,12 @@ SMFV_API int smfv_plan_stats(smfv_plan_t plan, double out[SMFV_PLAN_STATS])
     return SMFV_OK;
 }
 
-SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx,
-                               const double *d_values, const double *d_X, int64_t ldx,
-                               double *d_Y, int64_t ldy, void *stream)
+// The launch sequence of a plan.  ep == NULL: Y = A X, the instances and
+// arguments smfv_plan_execute has always launched.  ep != NULL (a fused
+// plan, smfv_plan_execute_axpby): the same branches with the *_axpby
+// instances, which apply alpha / beta in their stores.
+static int plan_launch(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx, const double *d_values,
+                       const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, void *stream, const Axpby *ep)
 {
     SMFV_REQUIRE(plan, "null plan");
     const int m = plan->m, K = plan->K;
@@ -2934,8 +3169,9 @@ SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int
     if (plan->sub) {
         // (r4) the whole rows by their plan, then the cut rows' partial sums
         // (each alone on the merge path: one row, its part of the range)
-        const int rc = smfv_plan_execute(plan->sub, d_row_ptr, d_col_idx, d_values, d_X, ldx,
-                                         d_Y + (int64_t)plan->sub_row * ldy, ldy, stream);
+        SMFV_REQUIRE(!ep, "internal: a NONZERO range has no fused epilogue");
+        const int rc = plan_launch(plan->sub, d_row_ptr, d_col_idx, d_values, d_X, ldx,
+                                   d_Y + (int64_t)plan->sub_row * ldy, ldy, stream, nullptr);
         if (rc) return rc;
         if (plan->ncut > 0) {  // one launch for both cut rows
             CutRows cr{};
@@ -2954,13 +3190,17 @@ SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int
     }
     if (!plan->tiled || (!plan->k1 && pick_vec(d_X, ldx, d_Y, ldy, K) != 2)) {
         // untiled: the row / merge kernels on the live values
+        SMFV_REQUIRE(!(ep && plan->variant == SMFV_NONZERO), "internal: NONZERO has no fused epilogue");
         if (plan->variant == SMFV_NONZERO)
             return launch_merge(plan->row_begin, m, plan->nnz_base, plan->nnz_end, d_row_ptr, d_col_idx, d_values,
                                 d_X, ldx, K, d_Y, ldy, plan->ws, plan->ws_bytes, st);
         if (plan->simple)
-            return launch_rows_simple(plan->row_begin, m, d_row_ptr, d_col_idx, d_values, d_X, ldx, K, d_Y, ldy, st);
-        return launch_rows(plan->row_begin, m, d_row_ptr, d_col_idx, d_values, d_X, ldx, plan->n, K, d_Y, ldy, st);
+            return launch_rows_simple(plan->row_begin, m, d_row_ptr, d_col_idx, d_values, d_X, ldx, K, d_Y, ldy, st,
+                                      ep);
+        return launch_rows(plan->row_begin, m, d_row_ptr, d_col_idx, d_values, d_X, ldx, plan->n, K, d_Y, ldy, st, ep);
     }
+    // (a fused plan is none of the three below: smfv::plan_create)
+    SMFV_REQUIRE(!(ep && (plan->k1 || plan->mfma || plan->wsn || plan->fma)), "internal: plan has no fused epilogue");
     if (!plan->live && d_values != plan->bound_values) {
         set_error("tiled plan: values not bound (call smfv_plan_bind_values with these d_values)");
         return SMFV_ERR_INVALID;
@@ -3036,14 +3276,25 @@ SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int
                 // more: the untiled row kernel on the same live values, as the
                 // wsn branch does (bit-identical: each row in CSR order)
                 return launch_rows(plan->row_begin, m, d_row_ptr, d_col_idx, d_values, d_X, ldx, plan->n, K, d_Y,
-                                   ldy, st);
+                                   ldy, st, ep);
             }
             // the value pairs come from the block's CSR values through a
             // range-checked buffer (the last odd row's read past the end gives 0)
-            hipLaunchKernelGGL(pick_ws_live(plan->ws_geom, plan->fma, narrow), dim3((unsigned)blocks),
+            if (ep)
+                hipLaunchKernelGGL(pick_ws_axpby_live(plan->ws_geom, narrow), dim3((unsigned)blocks),
+                                   dim3((unsigned)threads), 0, st, xr, narrow ? 1 : K / TILE_KP, chunked,
+                                   plan->ws_grec, plan->ws_lrec, plan->ws_loff, d_values + plan->nnz_base, d_X, ldx,
+                                   d_Y, ldy, plan->ws_vidx, plan->ws_vstride, (unsigned)(plan->nnz * 8), ep->alpha,
+                                   ep->beta);
+            else
+                hipLaunchKernelGGL(pick_ws_live(plan->ws_geom, plan->fma, narrow), dim3((unsigned)blocks),
+                                   dim3((unsigned)threads), 0, st, xr, narrow ? 1 : K / TILE_KP, chunked,
+                                   plan->ws_grec, plan->ws_lrec, plan->ws_loff, d_values + plan->nnz_base, d_X, ldx,
+                                   d_Y, ldy, plan->ws_vidx, plan->ws_vstride, (unsigned)(plan->nnz * 8));
+        } else if (ep) {
+            hipLaunchKernelGGL(pick_ws_axpby(plan->ws_geom, saddr, narrow), dim3((unsigned)blocks),
                                dim3((unsigned)threads), 0, st, xr, narrow ? 1 : K / TILE_KP, chunked, plan->ws_grec,
-                               plan->ws_lrec, plan->ws_loff, d_values + plan->nnz_base, d_X, ldx, d_Y, ldy,
-                               plan->ws_vidx, plan->ws_vstride, (unsigned)(plan->nnz * 8));
+                               plan->ws_lrec, plan->ws_loff, plan->tvals, d_X, ldx, d_Y, ldy, ep->alpha, ep->beta);
         } else {
             hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)threads), 0, st, xr,
                                narrow ? 1 : K / TILE_KP, chunked, plan->ws_grec, plan->ws_lrec, plan->ws_loff,
@@ -3051,7 +3302,13 @@ SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int
         }
         SMFV_LAUNCHED();
     }
-    if (plan->ndirect > 0) {
+    if (plan->ndirect > 0 && ep) {
+        hipLaunchKernelGGL(k_rows_list_axpby, dim3((unsigned)((plan->ndirect + 31) / 32), (unsigned)std::max(1, K / TILE_KP)),
+                           dim3(256), 0, st, plan->ndirect, K < TILE_KP ? K : 0, plan->direct_rows, plan->direct_off,
+                           plan->row_begin, d_row_ptr, d_col_idx, plan->live ? d_values : plan->tvals, d_X, ldx, d_Y, ldy,
+                           ep->alpha, ep->beta);
+        SMFV_LAUNCHED();
+    } else if (plan->ndirect > 0) {
         hipLaunchKernelGGL(k_rows_list, dim3((unsigned)((plan->ndirect + 31) / 32), (unsigned)std::max(1, K / TILE_KP)),
                            dim3(256), 0, st, plan->ndirect, K < TILE_KP ? K : 0, plan->direct_rows, plan->direct_off, plan->row_begin,
                            d_row_ptr, d_col_idx, plan->live ? d_values : plan->tvals, d_X, ldx, d_Y, ldy);
@@ -3060,6 +3317,48 @@ SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int
     return SMFV_OK;
 }
 
+SMFV_API int smfv_plan_execute(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx,
+                               const double *d_values, const double *d_X, int64_t ldx,
+                               double *d_Y, int64_t ldy, void *stream)
+{
+    return plan_launch(plan, d_row_ptr, d_col_idx, d_values, d_X, ldx, d_Y, ldy, stream, nullptr);
+}
+
+SMFV_API int smfv_plan_execute_axpby(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_idx,
+                                     const double *d_values, const double *d_X, int64_t ldx,
+                                     double alpha, double beta, double *d_Y, int64_t ldy, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    SMFV_REQUIRE(plan->epilogue != 0, "plan was created without SMFV_PLAN_AXPBY");
+    const int m = plan->m, K = plan->K;
+    SMFV_REQUIRE(ldx >= K && ldy >= K, "leading dimension smaller than K");
+    if (m == 0 || K == 0) return SMFV_OK;
+    SMFV_REQUIRE(d_Y, "null Y");
+    const Axpby ep{alpha, beta};
+    if (plan->epilogue == 1)
+        return plan_launch(plan, d_row_ptr, d_col_idx, d_values, d_X, ldx, d_Y, ldy, stream, &ep);
+    // two-pass: the plan's own launches into its scratch (ld = K), then k_axpby
+    const int rc = plan_launch(plan, d_row_ptr, d_col_idx, d_values, d_X, ldx, plan->ax_scratch, K, stream, nullptr);
+    if (rc) return rc;
+    const int vec = (K % 2 == 0 && ldy % 2 == 0 && aligned16(d_Y)) ? 2 : 1;
+    const int64_t nblk = ((int64_t)m * (K / vec) + 255) / 256;
+    SMFV_REQUIRE(nblk <= 0x7fffffff, "too many elements for one launch");
+    if (vec == 2)
+        hipLaunchKernelGGL(k_axpby<2>, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), (int64_t)m, K,
+                           plan->ax_scratch, d_Y, ldy, alpha, beta);
+    else
+        hipLaunchKernelGGL(k_axpby<1>, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), (int64_t)m, K,
+                           plan->ax_scratch, d_Y, ldy, alpha, beta);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_plan_epilogue_mode(smfv_plan_t plan, int *mode)
+{
+    SMFV_REQUIRE(plan && mode, "null argument");
+    *mode = plan->epilogue;
+    return SMFV_OK;
+}
 
 SMFV_API int smfv_spmm_rowblock_f64(int row_begin, int row_end, int n, const int *d_row_ptr,
                                     const int *d_col_idx, const double *d_values,

@@ -121,7 +121,10 @@ PLAN_WS_GEOM1, PLAN_WS_GEOM2, PLAN_WS_GEOM3 = 1024, 2048, 4096
 PLAN_LIVE_VALUES = 8192  # (r5) the tiled kernel reads the live CSR values (no snapshot, no bind)
 PLAN_SINGLE_ROWS = 16384  # (r5) one row per k_rows_ws team (no row pairs; A/B)
 PLAN_ROW_PAIRS = 32768  # (r5) row pairs forced (without either: the plan with fewer rounds)
+PLAN_AXPBY = 65536  # the plan runs Y = alpha*A*X + beta*Y (smfv_plan_execute_axpby)
+PLAN_AXPBY_TWO_PASS = 131072  # ... in the two-pass form (A/B, tests); implies PLAN_AXPBY
 PLAN_STATS = 18  # SMFV_PLAN_STATS
+EPILOGUE_MODES = {0: None, 1: "fused", 2: "two_pass"}  # smfv_plan_epilogue_mode
 PLAN_KERNELS = {0: None, 1: "k_rows_ws", 2: "k_rows_mfma", 3: "k_spmv_chunks", 5: "k_rows_wsn"}
 
 
@@ -141,16 +144,21 @@ class SpmmPlan:
     the block's rows to Y[0:end-begin]).  xcd_parts: "auto" (one row range
     per XCD when their X footprints allow it) or "one" (one wavefront cut in
     8 shares; SMFV_PLAN_ONE_WAVEFRONT, A/B).  The values snapshot of a tiled plan
-    is gathered on `stream`; a run() on another stream waits for it."""
+    is gathered on `stream`; a run() on another stream waits for it.
+    axpby: True makes the plan runnable with run_axpby() (Y = alpha*A*X +
+    beta*Y in place, SMFV_PLAN_AXPBY; the library fuses the epilogue into the
+    row kernels' stores where it can: epilogue_mode); "two_pass" forces the
+    scratch-and-second-pass form (SMFV_PLAN_AXPBY_TWO_PASS, A/B)."""
 
     def __init__(self, variant: int, A: DeviceCSR, K: int, tiles: str = "auto", fma: bool = False,
                  stream: torch.cuda.Stream | None = None, rows: tuple[int, int] | None = None,
                  seeds: str = "frontier", mfma: bool = False, split_ends: bool = False,
                  xcd_parts: str = "auto", tiled_kernel: str = "auto", live_values: bool = False,
-                 row_pairs: str = "auto"):
+                 row_pairs: str = "auto", axpby: bool | str = False):
         self.variant, self.A, self.K = Variant(variant), A, K
         self.rows = rows
         flags = {"auto": 0, "off": PLAN_NO_TILES, "force": PLAN_FORCE_TILES}[tiles]
+        flags |= {False: 0, True: PLAN_AXPBY, "two_pass": PLAN_AXPBY | PLAN_AXPBY_TWO_PASS}[axpby]
         if live_values:  # (r5) SMFV_PLAN_LIVE_VALUES: value pairs DMA'd from the CSR values, bind a no-op
             flags |= PLAN_LIVE_VALUES
         # (r5) row pairs in k_rows_ws tiles: "auto" (the plan whose busiest
@@ -208,6 +216,25 @@ class SpmmPlan:
         rp, ci, va = A.ptrs()
         call("smfv_plan_execute", self._plan, rp, ci, va, X.data_ptr(), ldx, Y.data_ptr(), ldy,
              stream_handle(stream))
+        return Y
+
+    @property
+    def epilogue_mode(self) -> str | None:
+        """None (no axpby), "fused" or "two_pass" (smfv_plan_epilogue_mode)."""
+        mode = ctypes.c_int(0)
+        call("smfv_plan_epilogue_mode", self._plan, byref(mode))
+        return EPILOGUE_MODES[mode.value]
+
+    def run_axpby(self, X: torch.Tensor, Y: torch.Tensor, alpha: float, beta: float,
+                  stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """Y = alpha * A * X + beta * Y in place (smfv_plan_execute_axpby); the
+        plan must have been created with axpby.  beta == 0 does not read Y."""
+        A, K = self.A, self.K
+        ldx = _check_dense(X, A.n, K, "X")
+        ldy = _check_dense(Y, self.m_out, K, "Y")
+        rp, ci, va = A.ptrs()
+        call("smfv_plan_execute_axpby", self._plan, rp, ci, va, X.data_ptr(), ldx,
+             ctypes.c_double(alpha), ctypes.c_double(beta), Y.data_ptr(), ldy, stream_handle(stream))
         return Y
 
     def __del__(self):
