@@ -414,8 +414,9 @@ __global__ __launch_bounds__(NT) void k_spmv_chunks(const int4 *__restrict__ hdr
 //    (LDS read of col/val, address arithmetic, loop control);
 //  * X is read through a buffer resource with a 32-bit byte offset
 //    (col * ldx * 8 + lane column) and the column-group step as the
-//    instruction's immediate offset (BUF = true, X < 4 GiB); BUF = false
-//    is the 64-bit pointer path for larger X;
+//    instruction's immediate offset (BUF = true: X rows * ldx * 8 <= 2^31 - 1,
+//    the offset being an int; launch_rows_mh); BUF = false is the 64-bit
+//    pointer path for larger X;
 //  * U non-zeros' X rows are in flight per team before they are accumulated
 //    in CSR order (separate multiply and add: bit-identical to the
 //    reference's sequential loop).

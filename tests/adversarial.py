@@ -30,6 +30,38 @@ LONG_ROWS = {100: 700, 2000: 1300}  # rows too wide for a tile: the direct list
 WIDE_ROW = 82  # the row [n-1, 0, n-1]
 
 
+# Leading dimensions (doubles, all even) of test_gpu_large_offsets.py: a
+# column window of a 3,000-row buffer with one of these strides spans n*ld*8
+# bytes, on a chosen side of the kernels' 2 GiB / 4 GiB addressing switches.
+LARGE_N = 3000
+LARGE_LD = {"A": 89478,    # just under 2^31: k_rows_mh's buffer form at its highest offsets
+            "B": 89480,    # just over 2^31: its 64-bit pointer form; k_rows_ws scalar-base form
+            "C": 178956,   # just under 2^32: scalar-base / wsn / live at their highest offsets
+            "D": 178958,   # just over 2^32: the dispatch flips; no offset reaches 2^32 yet
+            "E": 268436}   # 6 GiB: columns >= 2,000 lie beyond 2^32
+
+
+def large_offset_conditions(A):
+    """The conditions the large-offset cases rest on, for the pattern A (n =
+    LARGE_N): every span on its side of its threshold, and at least a quarter
+    of A's entries read X at a byte offset >= 2^31 with ld C, >= 2^32 with ld
+    E.  Returns the two shares."""
+    ld, n = LARGE_LD, LARGE_N
+    assert A.numCols == n and all(v % 2 == 0 for v in ld.values())
+    span = {k: n * v * 8 for k, v in ld.items()}
+    assert span["A"] <= 0x7fffffff < span["B"] < 1 << 32
+    assert 1 << 31 < span["C"] < 1 << 32 <= span["D"] < span["E"]
+    assert (1 << 32) - span["C"] < 2 * 8 * n and span["D"] - (1 << 32) < 2 * 8 * n  # two doubles a row from 2^32
+    assert 0x7fffffff - span["A"] < 2 * 8 * n and span["B"] - (1 << 31) < 2 * 8 * n
+    assert (n - 1) * ld["D"] * 8 < 1 << 32 < (n - 1) * ld["E"] * 8
+    off = A.colIndices.astype(np.int64) * 8
+    share_c = float(np.mean(off * ld["C"] >= 1 << 31))
+    share_e = float(np.mean(off * ld["E"] >= 1 << 32))
+    assert share_c >= 0.25 and share_e >= 0.25, (share_c, share_e)
+    assert (n - 1) * (ld["E"] - 1) * 8 >= 1 << 32  # the odd ld E - 1
+    return share_c, share_e
+
+
 def _csr(rows, vals_rng, m, n):
     rp = np.zeros(m + 1, np.int32)
     rp[1:] = np.cumsum([len(c) for c in rows])

@@ -189,3 +189,19 @@ def test_host_plans_verify_on_degenerate_shapes(m, n):
         assert w["tiles"] >= 1 and w["direct"] == 0 and w["entries"] >= A.nnz, (kw, w)
     c = _analyse_chunks(A, 0, m)
     assert c["fits"] and c["entries"] == A.nnz
+
+
+@pytest.mark.parametrize("kind", ["long", "short"])
+def test_large_offset_conditions(kind):
+    """What test_gpu_large_offsets.py rests on, without a GPU: each leading
+    dimension's span n * ld * 8 lies on the stated side of 2^31 / 2^32, and on
+    the patterns that file runs at least a quarter of the entries read X at a
+    byte offset >= 2^31 at ld C and >= 2^32 at ld E (uniform columns give a
+    half and a third)."""
+    A = adv.adv_pattern(M, N, SEED, adv.LONG_ROWS if kind == "long" else None)
+    share_c, share_e = adv.large_offset_conditions(A)
+    print("entry shares: >= 2^31 at C", share_c, ">= 2^32 at E", share_e)
+    assert 0.4 < share_c < 0.6 and 0.25 < share_e < 0.45
+    # the row block [1001, 2500) reads beyond 2^32 at E as well
+    s, e = int(A.rowPtr[1001]), int(A.rowPtr[2500])
+    assert np.mean(A.colIndices[s:e].astype(np.int64) * adv.LARGE_LD["E"] * 8 >= 1 << 32) >= 0.25

@@ -1088,23 +1088,43 @@ def test_live_values_x_over_4gib(gpu):
     kernel on the same live values instead of failing: bit-identical to the
     untiled plan, and to the snapshot plan (whose non-SADDR instance takes
     such an X).  A 27-point stencil of 4,000 rows whose X has 16.8 M rows
-    (4.3 GB): its columns touch the first 4,000 only."""
+    (4.3 GB).  Its columns are spread over all of X: c -> c * (n // 4000) for
+    c < 3,000 (byte offsets up to 3.2 GB) and the last 1,000 onto the last
+    1,000 rows of X, all of which start beyond 4 GiB (c * (n // 4000) alone
+    ends 1.4 MB short of 2^32).  All three plans are compared with a host loop
+    (adversarial.ref_f64) over the 4,000 X rows referenced, copied back from
+    the device -- fill_x_hash's values are small integers -- and with one
+    another."""
+    import adversarial as adv
     B = smfv.gen_fem27(4000, 16, 16, 0.83, 7)
     K = 32
     n = (1 << 32) // (8 * K) + 1024
-    A = smfv.SparseMatrix(B.values, B.colIndices, B.rowPtr, B.numRows, n)
+    c = np.arange(4000, dtype=np.int64)
+    cmap = np.where(c < 3000, c * (n // 4000), n - 4000 + c)
+    assert np.all(np.diff(cmap) > 0) and cmap[-1] == n - 1
+    assert 1 << 31 < cmap[2999] * K * 8 < 1 << 32 <= cmap[3000] * K * 8
+    cols = cmap[B.colIndices].astype(np.int32)
+    assert np.mean(cols.astype(np.int64) * K * 8 >= 1 << 32) > 0.2
+    A = smfv.SparseMatrix(B.values, cols, B.rowPtr, B.numRows, n)
     dA = smfv.DeviceCSR(A, gpu)
     dX = torch.empty((n, K), dtype=torch.float64, device=gpu)
     smfv.fill_x_hash(dX, 11)
+    Xh = dX[torch.from_numpy(cmap).to(gpu)].cpu().numpy()
+    assert np.all(Xh == np.rint(Xh)) and Xh.min() >= 1 and Xh.max() <= 100 and len(np.unique(Xh)) > 50
+    small = adv.Csr(np.asarray(B.values), np.asarray(B.colIndices), np.asarray(B.rowPtr), B.numRows, 4000)
+    Yref = adv.ref_f64(small, Xh)
     live = smfv.SpmmPlan(smfv.Variant.ROWWISE, dA, K, live_values=True, tiles="force")
     snap = smfv.SpmmPlan(smfv.Variant.ROWWISE, dA, K, tiles="force")
     ref = smfv.SpmmPlan(smfv.Variant.SEQUENTIAL, dA, K, tiles="off")
     assert live.stats()["live_values"] and live.stats()["tiled"]
+    assert snap.stats()["tiled"] and not snap.stats()["live_values"] and not ref.stats()["tiled"]
     Y = {k: torch.full((A.numRows, K), np.nan, dtype=torch.float64, device=gpu) for k in ("live", "snap", "ref")}
     live.run(dX, Y["live"])
     snap.run(dX, Y["snap"])
     ref.run(dX, Y["ref"])
     torch.cuda.synchronize()
+    for k in Y:
+        assert np.array_equal(bits(Y[k].cpu().numpy()), bits(Yref)), k
     assert torch.equal(Y["live"].view(torch.int64), Y["ref"].view(torch.int64))
     assert torch.equal(Y["snap"].view(torch.int64), Y["ref"].view(torch.int64))
     # the live values are read at every execute (no bind)
@@ -1113,6 +1133,8 @@ def test_live_values_x_over_4gib(gpu):
     ref.run(dX, Y["ref"])
     torch.cuda.synchronize()
     assert torch.equal(Y["live"].view(torch.int64), Y["ref"].view(torch.int64))
+    small.values = -0.25 * small.values
+    assert np.array_equal(bits(Y["live"].cpu().numpy()), bits(adv.ref_f64(small, Xh)))
     del dX
 
 
