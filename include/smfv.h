@@ -144,7 +144,19 @@ SMFV_API int smfv_spmm_csr_f64(int variant, int m, int n, int64_t nnz,
  * Streams: create allocates device memory and synchronises; bind and execute
  * are asynchronous and graph-capturable.  An execute on a stream other than
  * the bind's waits for the bind's gather (hipStreamWaitEvent; while capturing
- * it requires the gather to have completed).  A plan is not thread-safe. */
+ * it requires the gather to have completed).  A capture of an execute while
+ * the gather is still running on another stream is refused with
+ * SMFV_ERR_INVALID before anything is launched; the caller's capture, of any
+ * capture mode, stays valid (the library asks for the gather's state in the
+ * relaxed mode), and after the bind's stream has been synchronised the same
+ * plan captures.  A bind issued while its stream is capturing becomes part of
+ * the graph: the gather runs at every replay, from the values the array holds
+ * then, while the plan counts those values as bound from the capture on.  An
+ * execute captured after it on the same stream is ordered by the graph; an
+ * eager execute with the values the graph bound last is accepted, and it is
+ * the caller who orders it after a replay (the replay's stream, an event or a
+ * synchronize), as for any work that follows a graph launch.  A plan is not
+ * thread-safe. */
 typedef struct smfv_plan_s *smfv_plan_t;
 #define SMFV_PLAN_NO_TILES 1
 #define SMFV_PLAN_FORCE_TILES 2

@@ -3212,10 +3212,21 @@ static int plan_launch(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_
         SMFV_HIP(hipStreamIsCapturing(st, &cs));
         if (cs == hipStreamCaptureStatusNone) {
             SMFV_HIP(hipStreamWaitEvent(st, plan->bind_ev, 0));
-        } else if (hipEventQuery(plan->bind_ev) != hipSuccess) {
-            set_error("tiled plan: the values snapshot (bound on another stream) is still in flight while "
-                      "capturing; synchronize the bind stream before capture");
-            return SMFV_ERR_INVALID;
+        } else {
+            // a query that answers "not ready" invalidates a capture of the
+            // global (default) mode: made in the relaxed mode, it leaves the
+            // caller's capture as it is whatever it answers
+            hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+            SMFV_HIP(hipThreadExchangeStreamCaptureMode(&mode));
+            const hipError_t ready = hipEventQuery(plan->bind_ev);
+            const hipError_t back = hipThreadExchangeStreamCaptureMode(&mode);
+            if (ready != hipSuccess) {
+                (void)hipGetLastError();  // (the query's answer is not a launch error of the next call)
+                set_error("tiled plan: the values snapshot (bound on another stream) is still in flight while "
+                          "capturing; synchronize the bind stream before capture");
+                return SMFV_ERR_INVALID;
+            }
+            SMFV_HIP(back);
         }
     }
     if (plan->k1) {
