@@ -247,6 +247,62 @@ typedef struct smfv_plan_s *smfv_plan_t;
  * runs and tests) and implies AXPBY. */
 #define SMFV_PLAN_AXPBY 65536
 #define SMFV_PLAN_AXPBY_TWO_PASS 131072
+/* Y = A^T X.  Accepted by smfv_plan_create only.  With it a plan created from
+ * the CSR of A (m x n; h_row_ptr and h_col_idx both required) computes
+ * Y[n x K] = A^T X[m x K]: what BiCG, QMR, LSQR / LSMR, the normal equations
+ * and the restriction of a multigrid prolongation need beside A X, from the
+ * one CSR the caller holds.  No atomics: create transposes the PATTERN once on
+ * the host (smfv_csr_transpose: a stable counting sort) and the plan runs the
+ * row kernels of this library on it.
+ *
+ * Order of summation: Y[c, :] starts from s = 0.0, then s = s + values[j] *
+ * X[row(j), :] over all CSR indices j with col_idx[j] == c, in ascending j,
+ * multiply and add rounded separately -- the reference's sequential loop
+ * (SC/SparseMatrixFatVectorMultiply.cpp:17-27) on the CSR of A^T obtained by
+ * a stable counting sort of A's entries by column.  Repeated columns inside a
+ * row of A stay in their CSR order; a column with no entry gives +0.0, and it
+ * is written.  SEQUENTIAL / ROWWISE / COLUMNWISE: bit-identical to that loop,
+ * NaN for NaN and the sign of zero included.  NONZERO: |Y - Yref| <= 1e-12 *
+ * sum|a||x| + 1e-300 elementwise, and bit-identical where its inner plan takes
+ * the tiled kernel, as without the flag.  SMFV_PLAN_FMA / SMFV_PLAN_MFMA keep
+ * their documented looser contracts.
+ *
+ * Execute: d_X is m x K, d_Y is n x K; d_row_ptr / d_col_idx are ignored and
+ * may be NULL (the plan owns the transposed pattern); d_values is A's values
+ * array in A's order.
+ *
+ * Values contract: EVERY transposed plan computes from a plan-owned copy of
+ * the values in transposed order, written by smfv_plan_bind_values
+ * (k_permute_vals, then the inner plan's own gather from that copy) -- untiled
+ * and SMFV_PLAN_LIVE_VALUES plans too ("live" then means that the tiled
+ * kernel DMAs from that copy, with no tile snapshot).  So every transposed
+ * plan must be bound after the values change, and a bind is never a no-op.
+ * Execute refuses with SMFV_ERR_INVALID, before anything is launched, a
+ * d_values other than the bound pointer and an execute before any bind.
+ *
+ * Streams: as for tiled plans (above): bind and execute are asynchronous and
+ * capturable, a bind captured into a graph re-gathers at every replay, an
+ * execute on a stream other than the bind's waits for the bind, and while
+ * capturing the in-flight check is made in the relaxed mode and leaves the
+ * caller's capture valid.
+ *
+ * With SMFV_PLAN_AXPBY: Y <- alpha A^T X + beta Y by smfv_plan_execute_axpby,
+ * the formula, the beta == 0 rule and fused against two-pass exactly as
+ * documented there; smfv_plan_epilogue_mode reports the inner plan's mode.
+ * All other flags act on the transposed pattern (tiles on / off / forced,
+ * geometries, row pairs, seeds, XCD parts, FMA, MFMA, SIMPLE_ROWS).
+ * smfv_plan_stats reports the inner plan's figures, [4] including the
+ * transposed pattern, permutation and values, [8] the transposition.
+ *
+ * Refused with SMFV_ERR_INVALID and a message, before any device allocation:
+ * the flag in smfv_plan_create_rows and in every smfv_dist_plan_create*; a
+ * NULL h_row_ptr or h_col_idx; a column index outside [0, n).
+ *
+ * Out of scope: the plan-less smfv_spmm_* family, row-block and distributed
+ * plans, the C++ drop-in and the CLI (the reference has no such call),
+ * bench.py, and half-stored symmetric matrices (A^T of the stored half is not
+ * the other half's product). */
+#define SMFV_PLAN_TRANSPOSE 262144
 SMFV_API int smfv_plan_create(smfv_plan_t *plan, int variant, int m, int n, int64_t nnz,
                               const int *h_row_ptr, const int *h_col_idx, int K, int flags);
 /* Plan of the row block [row_begin, row_end) of a CSR matrix (h_row_ptr /
@@ -366,6 +422,19 @@ SMFV_API int smfv_plan_epilogue_mode(smfv_plan_t plan, int *mode);
  * rows summed as a team's second row (SMFV_PLAN_SINGLE_ROWS) */
 #define SMFV_PLAN_STATS 18
 SMFV_API int smfv_plan_stats(smfv_plan_t plan, double out[SMFV_PLAN_STATS]);
+/* *flag = 1 for a plan created with SMFV_PLAN_TRANSPOSE, else 0. */
+SMFV_API int smfv_plan_is_transposed(smfv_plan_t plan, int *flag);
+/* The CSR pattern of A^T (n rows, m columns) from the CSR pattern of A (m x
+ * n), as SMFV_PLAN_TRANSPOSE plans build it: a stable counting sort of A's
+ * entries by column, O(nnz + m + n), on the host (no device needed).
+ * t_row_ptr[n + 1]; for transposed entry j, t_col_idx[j] is its row in A and
+ * t_perm[j] its CSR index in A (values of A^T: values[t_perm[j]]), ascending
+ * inside every transposed row.  Every column index is validated before it is
+ * used (SMFV_ERR_INVALID for one outside [0, n), or a row_ptr that does not
+ * start at 0 or decreases), and the result is verified by replay before it is
+ * returned. */
+SMFV_API int smfv_csr_transpose(int m, int n, const int *h_row_ptr, const int *h_col_idx, int *t_row_ptr,
+                                int *t_col_idx, int *t_perm);
 SMFV_API int smfv_plan_destroy(smfv_plan_t plan);
 
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,

@@ -2,6 +2,7 @@
 AlexisBalayre/SparseMatrixMultiplicationMPI).
 
     Y[m x K] = A_csr[m x n] * X[n x K]   (fp64)
+    Y[n x K] = A_csr^T * X[m x K]        (transposed plans, spmm_t)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -14,6 +15,7 @@ from .inputs import (  # noqa: F401
     SparseMatrix,
     areMatricesEqual,
     cop20k_surrogate,
+    csr_transpose,
     deserialize,
     gen_fem27,
     gen_random_rows,
@@ -34,6 +36,7 @@ from .engine import (  # noqa: F401
     sparseMatrixFatVectorMultiplyNonZeroElement,
     sparseMatrixFatVectorMultiplyRowWise,
     spmm,
+    spmm_t,
 )
 
 __version__ = "0.1.0"

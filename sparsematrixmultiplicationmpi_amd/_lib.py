@@ -68,6 +68,8 @@ _SIGS = {
     "smfv_plan_epilogue_mode": (c_int, [c_void_p, _PI]),
     "smfv_plan_stats": (c_int, [c_void_p, _PD]),
     "smfv_plan_destroy": (c_int, [c_void_p]),
+    "smfv_plan_is_transposed": (c_int, [c_void_p, _PI]),
+    "smfv_csr_transpose": (c_int, [c_int, c_int, _PI, _PI, _PI, _PI, _PI]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_spmm_colpanel_f64": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

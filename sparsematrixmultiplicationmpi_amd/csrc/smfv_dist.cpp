@@ -639,6 +639,7 @@ static int dist_plan_create(smfv_dist_plan_t *out, smfv_comm_t comm, int p, int 
                             int flags)
 {
     SMFV_REQUIRE(out && h_row_ptr, "null plan / row_ptr");
+    SMFV_REQUIRE(!(flags & SMFV_PLAN_TRANSPOSE), "SMFV_PLAN_TRANSPOSE: distributed plans have no transposed form");
     SMFV_REQUIRE(p > 0 && rank >= 0 && rank < p, "bad rank %d of %d", rank, p);
     SMFV_REQUIRE(mode == SMFV_TO_ROOT || mode == SMFV_TO_ALL, "bad mode %d", mode);
     SMFV_REQUIRE(root >= 0 && root < p, "bad root %d", root);
@@ -710,6 +711,7 @@ SMFV_API int smfv_dist_plan_create_rowpart(smfv_dist_plan_t *out, smfv_comm_t co
                                            const int *h_row_ptr_local, const int *h_col_idx_local, int K, int flags)
 {
     SMFV_REQUIRE(out && comm && h_row_ptr_local, "null plan / communicator / row_ptr");
+    SMFV_REQUIRE(!(flags & SMFV_PLAN_TRANSPOSE), "SMFV_PLAN_TRANSPOSE: distributed plans have no transposed form");
     SMFV_REQUIRE(mode == SMFV_TO_ROOT || mode == SMFV_TO_ALL, "bad mode %d", mode);
     SMFV_REQUIRE(root >= 0 && root < comm->nranks, "bad root %d", root);
     SMFV_REQUIRE(m >= 0 && n >= 0 && K >= 0, "bad sizes");

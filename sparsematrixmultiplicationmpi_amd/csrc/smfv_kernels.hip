@@ -19,6 +19,10 @@
 //            Y = alpha A X + beta Y (smfv_plan_execute_axpby): the row kernels
 //            above with the epilogue in their stores, and the second pass of
 //            the plans that cannot fuse it; no counterpart in the reference
+//   k_permute_vals       Y = A^T X (SMFV_PLAN_TRANSPOSE): the bind's gather of
+//            A's values into the transposed pattern's order; the sums run on
+//            the kernels above over that pattern
+//            <- SC/SparseMatrixFatVectorMultiply.cpp:17-27 on the CSR of A^T
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -1620,6 +1624,30 @@ __global__ __launch_bounds__(256) void k_bind_items(int64_t n, const int2 *__res
     else reinterpret_cast<double *>(o + p0)[0] = a0;
     if (cnt > 2) reinterpret_cast<double *>(o + p1)[0] = a2;
 }
+
+// The bind of a SMFV_PLAN_TRANSPOSE plan: A's values into the order of the
+// transposed pattern, tv[j] = va[perm[j]] (perm from smfv::csr_transpose).
+// A lane produces two consecutive j: one 8-byte read of perm, two gathered
+// 8-byte loads, one 16-byte store (tv is 16-byte aligned, 2 * lane even); the
+// lane of an odd last entry takes the scalar path.  perm and tv are touched
+// once (non-temporal); the gathered loads are plain: neighbours in a
+// transposed row come from nearby rows of A and often share a line.  All
+// element offsets are 64-bit (nnz up to 2^31 - 1: byte offsets pass 2^32).
+typedef int perm_i2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void k_permute_vals(int64_t nnz, const int *__restrict__ perm,
+                                                      const double *__restrict__ va, double *__restrict__ tv)
+{
+    const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (j + 1 < nnz) {
+        const perm_i2 p = __builtin_nontemporal_load(reinterpret_cast<const perm_i2 *>(perm + j));
+        ws::d2 o;
+        o.x = va[(int64_t)p.x];
+        o.y = va[(int64_t)p.y];
+        __builtin_nontemporal_store(o, reinterpret_cast<ws::d2 *>(tv + j));
+    } else if (j < nnz) {
+        tv[j] = va[(int64_t)__builtin_nontemporal_load(perm + j)];
+    }
+}
 // (r4) The cut rows of a NONZERO range (at most its first and last row):
 // row i's partial sum over its entries [s[i], e[i]), one block per row.
 // With K <= 256 the block's lanes are G = 256 / K groups of K columns; group g
@@ -2429,9 +2457,21 @@ struct smfv_plan_s {
     int sub_row = 0;                       // the sub-plan's first row, block-local
     int ncut = 0, cut_row[2] = {0, 0};     // cut rows (global) and their nnz ranges
     int64_t cut_s[2] = {0, 0}, cut_e[2] = {0, 0};
+    // SMFV_PLAN_TRANSPOSE: this plan is a wrapper (m, n, nnz: A's).  It owns
+    // the transposed pattern, the values in that order (written by every bind,
+    // k_permute_vals) and the plan of A^T (n rows, m columns) that computes
+    // from them; bind_ev / bind_stream / bound_values above are the wrapper's
+    // own (the inner plan has its own for its snapshot)
+    smfv_plan_s *tr = nullptr;
+    int *t_rp = nullptr, *t_ci = nullptr, *t_perm = nullptr;
+    double *t_values = nullptr;
+    bool t_bound = false;                  // a bind has been issued
     ~smfv_plan_s()
     {
         delete sub;
+        delete tr;
+        for (void *q : {(void *)t_rp, (void *)t_ci, (void *)t_perm, (void *)t_values})
+            if (q) (void)hipFree(q);
         for (void *q : {(void *)tsrc, (void *)bind_items, (void *)tvals, (void *)ws_vidx, (void *)wsn_grec, (void *)wsn_lrec,
                         (void *)wsn_loff, (void *)ws_grec, (void *)ws_lrec, (void *)direct_rows,
                         (void *)direct_off, (void *)ws_loff, ws, (void *)ax_scratch, (void *)mf_rec, (void *)mf_ucols, (void *)mf_bstep,
@@ -2854,6 +2894,58 @@ int smfv::plan_create(smfv_plan_t *out, int variant, int row_begin, int m, int n
     return SMFV_OK;
 }
 
+// SMFV_PLAN_TRANSPOSE (include/smfv.h): the pattern of A^T from the host
+// (smfv::csr_transpose: validated, stable, replayed), a plan of it by
+// plan_create with the remaining flags, and the device arrays every execute
+// hands that plan: t_rp / t_ci, and t_values, which each bind fills through
+// t_perm.  Nothing is allocated on the device before the pattern is checked.
+static int plan_create_transposed(smfv_plan_t *out, int variant, int m, int n, int64_t nnz, const int *h_rp,
+                                  const int *h_ci, int K, int flags)
+{
+    const auto t_start = std::chrono::steady_clock::now();
+    std::vector<int> t_rp((size_t)n + 1), t_ci((size_t)nnz), t_perm((size_t)nnz);
+    std::string err;
+    if (!csr_transpose(m, n, h_rp, h_ci, t_rp.data(), t_ci.data(), t_perm.data(), &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    auto *p = new smfv_plan_s;
+    p->variant = variant;
+    p->m = m;
+    p->n = n;
+    p->K = K;
+    p->nnz_end = p->nnz = nnz;
+    int rc = plan_create(&p->tr, variant, 0, n, m, 0, nnz, t_rp.data(), t_ci.data(), K, flags & ~SMFV_PLAN_TRANSPOSE);
+    if (!rc) rc = upload(&p->t_rp, t_rp, p->dev_bytes);
+    if (!rc) rc = upload(&p->t_ci, t_ci, p->dev_bytes);
+    if (!rc) rc = upload(&p->t_perm, t_perm, p->dev_bytes);
+    if (!rc) {
+        const size_t b = std::max<size_t>((size_t)nnz, 1) * sizeof(double);
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->t_values), b);
+        if (e != hipSuccess) {
+            set_error("hipMalloc(transposed values): %s", hipGetErrorString(e));
+            rc = SMFV_ERR_HIP;
+        } else {
+            p->dev_bytes += b;
+        }
+    }
+    if (!rc) {
+        const hipError_t e = hipEventCreateWithFlags(&p->bind_ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            set_error("hipEventCreate: %s", hipGetErrorString(e));
+            rc = SMFV_ERR_HIP;
+        }
+    }
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    p->epilogue = p->tr->epilogue;
+    p->analysis_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    *out = p;
+    return SMFV_OK;
+}
+
 extern "C" {
 
 SMFV_API int smfv_plan_create(smfv_plan_t *out, int variant, int m, int n, int64_t nnz,
@@ -2862,14 +2954,36 @@ SMFV_API int smfv_plan_create(smfv_plan_t *out, int variant, int m, int n, int64
     SMFV_REQUIRE(out, "null plan pointer");
     SMFV_REQUIRE(variant >= SMFV_SEQUENTIAL && variant <= SMFV_NONZERO, "unknown variant %d", variant);
     SMFV_REQUIRE(m >= 0 && n >= 0 && nnz >= 0 && nnz <= 0x7fffffff && K >= 0, "bad sizes");
+    if (flags & SMFV_PLAN_TRANSPOSE)
+        SMFV_REQUIRE(h_row_ptr && h_col_idx, "SMFV_PLAN_TRANSPOSE needs the host row_ptr and col_idx");
     SMFV_REQUIRE(h_row_ptr == nullptr || (h_row_ptr[0] == 0 && h_row_ptr[m] == nnz), "row_ptr[0] != 0 or row_ptr[m] != nnz");
+    if (flags & SMFV_PLAN_TRANSPOSE) return plan_create_transposed(out, variant, m, n, nnz, h_row_ptr, h_col_idx, K, flags);
     return plan_create(out, variant, 0, m, n, 0, nnz, h_row_ptr, h_row_ptr ? h_col_idx : nullptr, K, flags);
+}
+
+SMFV_API int smfv_csr_transpose(int m, int n, const int *h_row_ptr, const int *h_col_idx, int *t_row_ptr,
+                                int *t_col_idx, int *t_perm)
+{
+    std::string err;
+    if (!csr_transpose(m, n, h_row_ptr, h_col_idx, t_row_ptr, t_col_idx, t_perm, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_plan_is_transposed(smfv_plan_t plan, int *flag)
+{
+    SMFV_REQUIRE(plan && flag, "null argument");
+    *flag = plan->tr ? 1 : 0;
+    return SMFV_OK;
 }
 
 SMFV_API int smfv_plan_create_rows(smfv_plan_t *out, int variant, int row_begin, int row_end, int n,
                                    const int *h_row_ptr, const int *h_col_idx, int K, int flags)
 {
     SMFV_REQUIRE(out && h_row_ptr, "null plan pointer / row_ptr");
+    SMFV_REQUIRE(!(flags & SMFV_PLAN_TRANSPOSE), "SMFV_PLAN_TRANSPOSE: row-block plans have no transposed form");
     SMFV_REQUIRE(variant >= SMFV_SEQUENTIAL && variant <= SMFV_NONZERO, "unknown variant %d", variant);
     SMFV_REQUIRE(row_begin >= 0 && row_end >= row_begin && n >= 0 && K >= 0, "bad row block [%d, %d)", row_begin,
                  row_end);
@@ -3043,6 +3157,26 @@ SMFV_API void smfv_set_analysis_threads(int threads) { smfv::analysis_threads = 
 SMFV_API int smfv_plan_bind_values(smfv_plan_t plan, const double *d_values, void *stream)
 {
     SMFV_REQUIRE(plan, "null plan");
+    if (plan->tr) {
+        // SMFV_PLAN_TRANSPOSE: the values into the transposed order, then the
+        // inner plan's own bind from them on the same stream (nothing for a
+        // live or untiled inner plan).  Never a no-op: every kernel of the
+        // inner plan, its run-time fallbacks included, reads t_values
+        SMFV_REQUIRE(d_values || plan->nnz == 0, "null values");
+        hipStream_t st = as_stream(stream);
+        if (plan->nnz > 0) {
+            hipLaunchKernelGGL(k_permute_vals, dim3((unsigned)((plan->nnz + 511) / 512)), dim3(256), 0, st, plan->nnz,
+                               plan->t_perm, d_values, plan->t_values);
+            SMFV_LAUNCHED();
+        }
+        const int rc = smfv_plan_bind_values(plan->tr, plan->t_values, stream);
+        if (rc) return rc;
+        SMFV_HIP(hipEventRecord(plan->bind_ev, st));
+        plan->bind_stream = st;
+        plan->bound_values = d_values;
+        plan->t_bound = true;
+        return SMFV_OK;
+    }
     if (plan->sub) return smfv_plan_bind_values(plan->sub, d_values, stream);  // (the cut rows read live values)
     if (!plan->tiled || plan->live) return SMFV_OK;  // (r5) live plans read the values at execute
     SMFV_REQUIRE(d_values || plan->nnz == 0, "null values");
@@ -3125,6 +3259,13 @@ SMFV_API int smfv_plan_destroy(smfv_plan_t plan)
 SMFV_API int smfv_plan_stats(smfv_plan_t plan, double out[SMFV_PLAN_STATS])
 {
     SMFV_REQUIRE(plan && out, "null argument");
+    if (plan->tr) {  // SMFV_PLAN_TRANSPOSE: the plan of A^T, plus the wrapper's arrays and the transposition
+        const int rc = smfv_plan_stats(plan->tr, out);
+        if (rc) return rc;
+        out[4] += (double)plan->dev_bytes;
+        out[8] = plan->analysis_ms;
+        return SMFV_OK;
+    }
     if (plan->sub) {  // a NONZERO range: its whole rows' plan describes it
         smfv_plan_stats(plan->sub, out);
         out[6] = plan->row_begin;
@@ -3153,6 +3294,47 @@ SMFV_API int smfv_plan_stats(smfv_plan_t plan, double out[SMFV_PLAN_STATS])
     return SMFV_OK;
 }
 
+// Order a launch on `st` after the bind recorded in `ev` on `bind_stream`.
+// Not capturing: a stream wait.  Capturing: the bind must have completed; a
+// query that answers "not ready" invalidates a capture of the global
+// (default) mode, so it is made in the relaxed mode, which leaves the caller's
+// capture as it is whatever it answers.
+static int order_after_bind(hipStream_t st, hipStream_t bind_stream, hipEvent_t ev, const char *what)
+{
+    if (st == bind_stream) return SMFV_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    SMFV_HIP(hipStreamIsCapturing(st, &cs));
+    if (cs == hipStreamCaptureStatusNone) {
+        SMFV_HIP(hipStreamWaitEvent(st, ev, 0));
+        return SMFV_OK;
+    }
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    SMFV_HIP(hipThreadExchangeStreamCaptureMode(&mode));
+    const hipError_t ready = hipEventQuery(ev);
+    const hipError_t back = hipThreadExchangeStreamCaptureMode(&mode);
+    if (ready != hipSuccess) {
+        (void)hipGetLastError();  // (the query's answer is not a launch error of the next call)
+        set_error("%s (bound on another stream) is still in flight while "
+                  "capturing; synchronize the bind stream before capture", what);
+        return SMFV_ERR_INVALID;
+    }
+    SMFV_HIP(back);
+    return SMFV_OK;
+}
+
+// SMFV_PLAN_TRANSPOSE: the checks of an execute on the wrapper, before
+// anything is launched -- the values are bound, and they are these -- then
+// the stream is ordered after the wrapper's bind (k_permute_vals and the inner
+// plan's gather).
+static int transposed_ready(smfv_plan_t plan, const double *d_values, hipStream_t st)
+{
+    if (!plan->t_bound || d_values != plan->bound_values) {
+        set_error("transposed plan: values not bound (call smfv_plan_bind_values with these d_values)");
+        return SMFV_ERR_INVALID;
+    }
+    return order_after_bind(st, plan->bind_stream, plan->bind_ev, "transposed plan: the values in transposed order");
+}
+
 // The launch sequence of a plan.  ep == NULL: Y = A X, the instances and
 // arguments smfv_plan_execute has always launched.  ep != NULL (a fused
 // plan, smfv_plan_execute_axpby): the same branches with the *_axpby
@@ -3161,6 +3343,14 @@ static int plan_launch(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_
                        const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, void *stream, const Axpby *ep)
 {
     SMFV_REQUIRE(plan, "null plan");
+    if (plan->tr) {
+        // Y[n x K] = A^T X[m x K]: the plan of A^T on the plan-owned pattern and
+        // values; the caller's d_row_ptr / d_col_idx are not read
+        SMFV_REQUIRE(ldx >= plan->K && ldy >= plan->K, "leading dimension smaller than K");
+        const int rc = transposed_ready(plan, d_values, as_stream(stream));
+        if (rc) return rc;
+        return plan_launch(plan->tr, plan->t_rp, plan->t_ci, plan->t_values, d_X, ldx, d_Y, ldy, stream, ep);
+    }
     const int m = plan->m, K = plan->K;
     SMFV_REQUIRE(ldx >= K && ldy >= K, "leading dimension smaller than K");
     if (m == 0 || K == 0) return SMFV_OK;
@@ -3206,28 +3396,10 @@ static int plan_launch(smfv_plan_t plan, const int *d_row_ptr, const int *d_col_
         set_error("tiled plan: values not bound (call smfv_plan_bind_values with these d_values)");
         return SMFV_ERR_INVALID;
     }
-    if (!plan->live && st != plan->bind_stream) {
+    if (!plan->live) {
         // the snapshot was gathered on another stream: order this launch after it
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        SMFV_HIP(hipStreamIsCapturing(st, &cs));
-        if (cs == hipStreamCaptureStatusNone) {
-            SMFV_HIP(hipStreamWaitEvent(st, plan->bind_ev, 0));
-        } else {
-            // a query that answers "not ready" invalidates a capture of the
-            // global (default) mode: made in the relaxed mode, it leaves the
-            // caller's capture as it is whatever it answers
-            hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-            SMFV_HIP(hipThreadExchangeStreamCaptureMode(&mode));
-            const hipError_t ready = hipEventQuery(plan->bind_ev);
-            const hipError_t back = hipThreadExchangeStreamCaptureMode(&mode);
-            if (ready != hipSuccess) {
-                (void)hipGetLastError();  // (the query's answer is not a launch error of the next call)
-                set_error("tiled plan: the values snapshot (bound on another stream) is still in flight while "
-                          "capturing; synchronize the bind stream before capture");
-                return SMFV_ERR_INVALID;
-            }
-            SMFV_HIP(back);
-        }
+        const int rc = order_after_bind(st, plan->bind_stream, plan->bind_ev, "tiled plan: the values snapshot");
+        if (rc) return rc;
     }
     if (plan->k1) {
         if (plan->ntiles > 0) {
@@ -3342,6 +3514,15 @@ SMFV_API int smfv_plan_execute_axpby(smfv_plan_t plan, const int *d_row_ptr, con
 {
     SMFV_REQUIRE(plan, "null plan");
     SMFV_REQUIRE(plan->epilogue != 0, "plan was created without SMFV_PLAN_AXPBY");
+    if (plan->tr) {
+        // SMFV_PLAN_TRANSPOSE: the inner plan's epilogue (fused, or two-pass
+        // through its own n x K scratch) on the plan-owned pattern and values
+        SMFV_REQUIRE(ldx >= plan->K && ldy >= plan->K, "leading dimension smaller than K");
+        const int rc = transposed_ready(plan, d_values, as_stream(stream));
+        if (rc) return rc;
+        return smfv_plan_execute_axpby(plan->tr, plan->t_rp, plan->t_ci, plan->t_values, d_X, ldx, alpha, beta, d_Y, ldy,
+                                       stream);
+    }
     const int m = plan->m, K = plan->K;
     SMFV_REQUIRE(ldx >= K && ldy >= K, "leading dimension smaller than K");
     if (m == 0 || K == 0) return SMFV_OK;

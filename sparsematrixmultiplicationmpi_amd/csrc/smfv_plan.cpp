@@ -1644,4 +1644,62 @@ bool build_wsn_plan(int m, int n, const int *rp, const int *ci, int kw, WsnPlan 
     return any;
 }
 
+// The CSR of A^T by a stable counting sort of A's entries by column: the
+// entries of one column keep their CSR order in A, which is the summation
+// order SMFV_PLAN_TRANSPOSE documents (include/smfv.h).  Every row_ptr step
+// and column index is checked before anything is written through it, and the
+// result is replayed against A before it is returned.
+bool csr_transpose(int m, int n, const int *rp, const int *ci, int *t_rp, int *t_ci, int *t_perm, std::string *err)
+{
+    auto fail = [&](const char *fmt, long long a, long long b) {
+        if (err) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, fmt, a, b);
+            *err = buf;
+        }
+        return false;
+    };
+    if (m < 0 || n < 0) return fail("transpose: bad sizes %lld x %lld", m, n);
+    if (!rp || !t_rp) return fail("transpose: null row_ptr (%lld x %lld)", m, n);
+    if (rp[0] != 0) return fail("transpose: row_ptr[0] = %lld, not %lld", rp[0], 0);
+    for (int r = 0; r < m; ++r)
+        if (rp[r + 1] < rp[r]) return fail("transpose: row_ptr decreases at row %lld (%lld)", r, rp[r + 1]);
+    const int64_t nnz = rp[m];
+    if (nnz > 0 && (!ci || !t_ci || !t_perm)) return fail("transpose: null col_idx (%lld x %lld)", m, n);
+    // count (and validate) the columns: nothing is indexed by an unchecked one
+    std::vector<int64_t> next((size_t)n + 1, 0);
+    for (int64_t j = 0; j < nnz; ++j) {
+        const int c = ci[j];
+        if (c < 0 || c >= n) return fail("transpose: column index %lld outside [0, %lld)", c, n);
+        ++next[(size_t)c + 1];
+    }
+    for (int c = 0; c < n; ++c) next[(size_t)c + 1] += next[(size_t)c];
+    for (int c = 0; c <= n; ++c) t_rp[c] = (int)next[(size_t)c];
+    // scatter in CSR order: stable
+    for (int r = 0; r < m; ++r)
+        for (int64_t j = rp[r]; j < rp[r + 1]; ++j) {
+            const int64_t d = next[(size_t)ci[j]]++;
+            t_ci[d] = r;
+            t_perm[d] = (int)j;
+        }
+    // replay: t_perm a permutation of [0, nnz), ascending inside every
+    // transposed row; each entry in the transposed row of its column, naming
+    // the row of A that holds it
+    if (t_rp[0] != 0 || t_rp[n] != nnz) return fail("transpose: replay: row_ptr ends %lld, %lld", t_rp[0], t_rp[n]);
+    std::vector<uint8_t> seen((size_t)nnz, 0);
+    for (int c = 0; c < n; ++c) {
+        if (t_rp[c + 1] < t_rp[c]) return fail("transpose: replay: row_ptr decreases at %lld (%lld)", c, t_rp[c + 1]);
+        for (int64_t d = t_rp[c]; d < t_rp[c + 1]; ++d) {
+            const int64_t j = t_perm[d];
+            if (j < 0 || j >= nnz || seen[(size_t)j]) return fail("transpose: replay: entry %lld names %lld twice or out of range", d, j);
+            seen[(size_t)j] = 1;
+            if (ci[j] != c) return fail("transpose: replay: entry %lld sits in the wrong row (%lld)", d, c);
+            if (d > t_rp[c] && t_perm[d - 1] >= j) return fail("transpose: replay: entry %lld out of CSR order (%lld)", d, j);
+            const int r = t_ci[d];
+            if (r < 0 || r >= m || j < rp[r] || j >= rp[r + 1]) return fail("transpose: replay: entry %lld names the wrong row %lld", d, r);
+        }
+    }
+    return true;
+}
+
 }  // namespace smfv

@@ -326,4 +326,16 @@ struct SpmvChunkPlan {
 bool build_spmv_chunks(int m, int n, const int *row_ptr, const int *col_idx, int cap, int maxrows,
                        SpmvChunkPlan &out, std::string *err, bool allow_wide = true);
 
+// The pattern of A^T (n rows, m columns) for SMFV_PLAN_TRANSPOSE plans: a
+// stable counting sort of A's CSR entries by column, O(nnz + m + n).
+// t_row_ptr[n + 1]; t_col_idx[j] is the row of A that holds transposed entry
+// j and t_perm[j] its CSR index in A, ascending inside every transposed row
+// (so a row of A^T is summed in A's CSR order, repeated columns of a row of A
+// included).  row_ptr and every column index are validated before anything is
+// written through them; the result is verified by replay (t_perm a
+// permutation, every entry in its column's row and naming its own row of A,
+// ascending order).  false (with *err) on a bad input or a failed replay.
+bool csr_transpose(int m, int n, const int *row_ptr, const int *col_idx, int *t_row_ptr, int *t_col_idx,
+                   int *t_perm, std::string *err);
+
 }  // namespace smfv

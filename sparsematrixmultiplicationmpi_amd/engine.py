@@ -78,12 +78,14 @@ class DeviceCSR:
     def ptrs(self):
         return self.row_ptr.data_ptr(), self.col_idx.data_ptr(), self.values.data_ptr()
 
-    def plan(self, variant: int, K: int, stream: torch.cuda.Stream | None = None) -> "SpmmPlan":
-        """The cached plan of (variant, K), created (and bound on `stream`) on first use."""
-        key = (int(variant), int(K))
+    def plan(self, variant: int, K: int, stream: torch.cuda.Stream | None = None,
+             transpose: bool = False) -> "SpmmPlan":
+        """The cached plan of (variant, K) -- of A, or with `transpose` of A^T
+        (Y = A^T X) --, created (and bound on `stream`) on first use."""
+        key = (int(variant), int(K), True) if transpose else (int(variant), int(K))
         p = self._plans.get(key)
         if p is None:
-            p = self._plans[key] = SpmmPlan(variant, self, K, stream=stream)
+            p = self._plans[key] = SpmmPlan(variant, self, K, stream=stream, transpose=transpose)
         elif p.bound_version != self.values_version():
             p.bind_values(stream)  # values changed since the bind: snapshot them again
         return p
@@ -123,6 +125,7 @@ PLAN_SINGLE_ROWS = 16384  # (r5) one row per k_rows_ws team (no row pairs; A/B)
 PLAN_ROW_PAIRS = 32768  # (r5) row pairs forced (without either: the plan with fewer rounds)
 PLAN_AXPBY = 65536  # the plan runs Y = alpha*A*X + beta*Y (smfv_plan_execute_axpby)
 PLAN_AXPBY_TWO_PASS = 131072  # ... in the two-pass form (A/B, tests); implies PLAN_AXPBY
+PLAN_TRANSPOSE = 262144  # the plan computes Y = A^T X from A's CSR (SMFV_PLAN_TRANSPOSE)
 PLAN_STATS = 18  # SMFV_PLAN_STATS
 EPILOGUE_MODES = {0: None, 1: "fused", 2: "two_pass"}  # smfv_plan_epilogue_mode
 PLAN_KERNELS = {0: None, 1: "k_rows_ws", 2: "k_rows_mfma", 3: "k_spmv_chunks", 5: "k_rows_wsn"}
@@ -148,15 +151,25 @@ class SpmmPlan:
     axpby: True makes the plan runnable with run_axpby() (Y = alpha*A*X +
     beta*Y in place, SMFV_PLAN_AXPBY; the library fuses the epilogue into the
     row kernels' stores where it can: epilogue_mode); "two_pass" forces the
-    scratch-and-second-pass form (SMFV_PLAN_AXPBY_TWO_PASS, A/B)."""
+    scratch-and-second-pass form (SMFV_PLAN_AXPBY_TWO_PASS, A/B).
+    transpose: True plans Y[A.n x K] = A^T X[A.m x K] (SMFV_PLAN_TRANSPOSE):
+    the pattern is transposed once on the host and every other argument acts
+    on the transposed pattern; the sums run in A's CSR order per column, so
+    the result is bit-identical to the sequential loop on the CSR of A^T.
+    Every transposed plan computes from a plan-owned copy of the values in
+    transposed order, so it must be bound again whenever the values change
+    (untiled and live_values plans too).  Not with rows=."""
 
     def __init__(self, variant: int, A: DeviceCSR, K: int, tiles: str = "auto", fma: bool = False,
                  stream: torch.cuda.Stream | None = None, rows: tuple[int, int] | None = None,
                  seeds: str = "frontier", mfma: bool = False, split_ends: bool = False,
                  xcd_parts: str = "auto", tiled_kernel: str = "auto", live_values: bool = False,
-                 row_pairs: str = "auto", axpby: bool | str = False):
+                 row_pairs: str = "auto", axpby: bool | str = False, transpose: bool = False):
+        if transpose and rows is not None:
+            raise ValueError("transpose=True has no row-block form (rows=)")
         self.variant, self.A, self.K = Variant(variant), A, K
         self.rows = rows
+        self._transposed = bool(transpose)
         flags = {"auto": 0, "off": PLAN_NO_TILES, "force": PLAN_FORCE_TILES}[tiles]
         flags |= {False: 0, True: PLAN_AXPBY, "two_pass": PLAN_AXPBY | PLAN_AXPBY_TWO_PASS}[axpby]
         if live_values:  # (r5) SMFV_PLAN_LIVE_VALUES: value pairs DMA'd from the CSR values, bind a no-op
@@ -180,12 +193,14 @@ class SpmmPlan:
         # (SMFV_PLAN_WS_GEOM1 / 2 / 3)
         flags |= {"auto": 0, "ws": PLAN_WS, "ws1": PLAN_WS | PLAN_WS_GEOM1,
                   "ws2": PLAN_WS | PLAN_WS_GEOM2, "ws3": PLAN_WS | PLAN_WS_GEOM3}[tiled_kernel]
+        if transpose:
+            flags |= PLAN_TRANSPOSE
         self._plan = ctypes.c_void_p()
         ip = ctypes.POINTER(ctypes.c_int)
         if rows is None:
             call("smfv_plan_create", byref(self._plan), int(variant), A.m, A.n, A.nnz,
                  A.h_row_ptr.ctypes.data_as(ip), A.h_col_idx.ctypes.data_as(ip), K, flags)
-            self.m_out = A.m
+            self.m_out = A.n if transpose else A.m
         else:
             r0, r1 = int(rows[0]), int(rows[1])
             call("smfv_plan_create_rows", byref(self._plan), int(variant), r0, r1, A.n,
@@ -197,6 +212,17 @@ class SpmmPlan:
         """(Re)bind a tiled plan to A's current device values (after they change)."""
         call("smfv_plan_bind_values", self._plan, self.A.values.data_ptr(), stream_handle(stream))
         self.bound_version = self.A.values_version()
+
+    @property
+    def transposed(self) -> bool:
+        """True for a plan of Y = A^T X (smfv_plan_is_transposed)."""
+        flag = ctypes.c_int(0)
+        call("smfv_plan_is_transposed", self._plan, byref(flag))
+        return bool(flag.value)
+
+    @property
+    def _x_rows(self) -> int:
+        return self.A.m if self._transposed else self.A.n
 
     def stats(self) -> dict:
         out = (ctypes.c_double * PLAN_STATS)()
@@ -211,7 +237,7 @@ class SpmmPlan:
 
     def run(self, X: torch.Tensor, Y: torch.Tensor, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         A, K = self.A, self.K
-        ldx = _check_dense(X, A.n, K, "X")
+        ldx = _check_dense(X, self._x_rows, K, "X")
         ldy = _check_dense(Y, self.m_out, K, "Y")
         rp, ci, va = A.ptrs()
         call("smfv_plan_execute", self._plan, rp, ci, va, X.data_ptr(), ldx, Y.data_ptr(), ldy,
@@ -230,7 +256,7 @@ class SpmmPlan:
         """Y = alpha * A * X + beta * Y in place (smfv_plan_execute_axpby); the
         plan must have been created with axpby.  beta == 0 does not read Y."""
         A, K = self.A, self.K
-        ldx = _check_dense(X, A.n, K, "X")
+        ldx = _check_dense(X, self._x_rows, K, "X")
         ldy = _check_dense(Y, self.m_out, K, "Y")
         rp, ci, va = A.ptrs()
         call("smfv_plan_execute_axpby", self._plan, rp, ci, va, X.data_ptr(), ldx,
@@ -254,6 +280,16 @@ def spmm(variant: int, A: DeviceCSR, X: torch.Tensor, Y: torch.Tensor | None = N
     if Y is None:
         Y = torch.empty((A.m, K), dtype=torch.float64, device=A.device)
     return A.plan(variant, K, stream).run(X, Y, stream)
+
+
+def spmm_t(variant: int, A: DeviceCSR, X: torch.Tensor, Y: torch.Tensor | None = None,
+           stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Y = A^T * X on the device (X: A.m x K, Y: A.n x K; asynchronous on
+    `stream`), through A's cached transposed plan for (variant, K)."""
+    K = X.shape[1]
+    if Y is None:
+        Y = torch.empty((A.n, K), dtype=torch.float64, device=A.device)
+    return A.plan(variant, K, stream, transpose=True).run(X, Y, stream)
 
 
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,

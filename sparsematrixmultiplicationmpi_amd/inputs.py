@@ -212,3 +212,20 @@ def permute_symmetric(A: SparseMatrix, perm: np.ndarray) -> SparseMatrix:
     order = np.lexsort((cols, rows))
     return SparseMatrix(values=np.asarray(A.values)[src][order], colIndices=cols[order].astype(np.int32),
                         rowPtr=nrp.astype(np.int32), numRows=m, numCols=m)
+
+
+def csr_transpose(A: SparseMatrix) -> tuple[SparseMatrix, np.ndarray]:
+    """(A^T as CSR, perm) by the library's stable counting sort
+    (smfv_csr_transpose, host only): entry j of A^T is entry perm[j] of A, and
+    the entries of a row of A^T keep A's CSR order -- the pattern and order a
+    transposed plan (SpmmPlan(..., transpose=True)) computes with."""
+    rp = np.ascontiguousarray(A.rowPtr, dtype=np.int32)
+    ci = np.ascontiguousarray(A.colIndices, dtype=np.int32)
+    if len(rp) != A.numRows + 1 or len(ci) != (int(rp[-1]) if len(rp) else 0):
+        raise ValueError("malformed rowPtr / colIndices")
+    nnz = len(ci)
+    t_rp = np.zeros(A.numCols + 1, np.int32)
+    t_ci, perm = np.zeros(nnz, np.int32), np.zeros(nnz, np.int32)
+    call("smfv_csr_transpose", A.numRows, A.numCols, _ip(rp), _ip(ci), _ip(t_rp), _ip(t_ci), _ip(perm))
+    return SparseMatrix(values=np.asarray(A.values, dtype=np.float64)[perm], colIndices=t_ci, rowPtr=t_rp,
+                        numRows=A.numCols, numCols=A.numRows), perm
