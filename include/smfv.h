@@ -437,6 +437,107 @@ SMFV_API int smfv_csr_transpose(int m, int n, const int *h_row_ptr, const int *h
                                 int *t_col_idx, int *t_perm);
 SMFV_API int smfv_plan_destroy(smfv_plan_t plan);
 
+/* ---- triangular solves: T Y = X with a fat right-hand side ----------------
+ * The preconditioner step of the block Krylov methods the plans above serve
+ * (Gauss-Seidel / SSOR sweeps, ILU(0) / IC(0) factors, multigrid smoothers).
+ * T is the lower triangle (SMFV_TRSM_UPPER: the upper) of a square m x m CSR
+ * matrix the caller already holds; X and Y are m x K, row-major, ldx, ldy >=
+ * K, fp64.  No atomics, a fixed launch sequence, the same bits on every run.
+ *
+ * Semantics.  A lower solve takes the rows i = 0 .. m-1; an upper solve
+ * mirrors it (rows descend, the strict entries are those with c > i).  For
+ * every column k:
+ *     s = X[i,k]
+ *     for j in row i's CSR entries, ascending j:   c = col_idx[j]
+ *         c <  i : s = fl(s - fl(values[j] * Y[c,k]))   separate multiply and
+ *                                                       subtract, never an FMA
+ *         c == i : d = values[j] for the first such entry,
+ *                  d = fl(d + values[j]) for each later one
+ *         c >  i : ignored (the other triangle)
+ *     Y[i,k] = fl(s / d)      a true IEEE division, not a reciprocal multiply
+ *     Y[i,k] = s              SMFV_TRSM_UNIT_DIAG: entries with c == i are
+ *                             ignored too
+ * The result is bit-identical to this sequential substitution, NaN for NaN
+ * and the sign of zero included; NaN, inf, signed zeros and subnormals
+ * propagate exactly as in the loop.
+ *   - The whole matrix is accepted: the other triangle is ignored, so with A
+ *     itself `lower` is the forward Gauss-Seidel sweep (D + L)^-1 X and
+ *     `upper` the backward one.
+ *   - Unsorted rows and repeated columns are legal: repeated strict entries
+ *     each subtract, in CSR order; repeated diagonal entries are summed in CSR
+ *     order.
+ *   - A zero or non-finite pivot gives what IEEE gives (+-inf, NaN), written
+ *     without any check or synchronisation.
+ *   - In place: d_Y == d_X with ldy == ldx is allowed (each element is read
+ *     and written by the same lane); any other overlap is undefined.
+ *   - Columns beyond K (padding) are neither read nor written.
+ *   - T^T Y = X (the second half of IC) is not a flag: smfv_csr_transpose
+ *     gives the caller the CSR of the other triangle (values: values[t_perm]),
+ *     and a plan of that solves it.
+ *   - Out of scope: distributed plans, the C++ drop-in, the CLI, bench.py.
+ *
+ * Refused at create with SMFV_ERR_INVALID and a message, before any device
+ * allocation: a row with no diagonal entry without SMFV_TRSM_UNIT_DIAG (the
+ * message names the first such row), a column index outside [0, m), K < 1,
+ * NO_CHAIN together with CHAIN_ALL, unknown flag bits.
+ *
+ * Execution is level-scheduled: level(i) = 1 + the highest level
+ * among the rows that row i's strict entries name.  A level of more than
+ * `thin` rows is one grid launch (k_trsm_level); a maximal run of consecutive
+ * levels of <= thin rows is one launch of a single 1024-lane block that walks
+ * them with a block barrier in between (k_trsm_chain).  A dependency crosses
+ * between workgroups only at a kernel boundary: no flags, no spinning, no
+ * cooperative launch.  The schedule never changes the arithmetic: every
+ * setting below gives the same bits.
+ *
+ * Values contract (that of the transposed plans): bind copies A's values
+ * into plan order (k_permute_vals) and writes each row's pivot d; the plan
+ * computes from that copy until the next bind, so bind again after the values
+ * change.  Execute refuses with SMFV_ERR_INVALID, before anything is
+ * launched, a plan never bound and a d_values other than the bound pointer.
+ * The pattern must not change over a plan's life.
+ *
+ * Streams (as for tiled plans): create allocates device memory and
+ * synchronises; bind and execute are asynchronous and graph-capturable -- no
+ * allocation, no synchronisation, no host read-back.  An execute on a stream
+ * other than the bind's waits for the bind; while capturing, the bind must
+ * have completed, which is asked in the relaxed capture mode, so a refusal
+ * leaves the caller's capture valid.  A bind captured into a graph gathers
+ * again at every replay.  A plan is not thread-safe. */
+typedef struct smfv_trsm_plan_s *smfv_trsm_plan_t;
+#define SMFV_TRSM_UPPER 1      /* default: lower */
+#define SMFV_TRSM_UNIT_DIAG 2
+#define SMFV_TRSM_NO_CHAIN 4   /* every level its own launch (A/B, tests) */
+#define SMFV_TRSM_CHAIN_ALL 8  /* all levels in the one-block kernel, one launch (A/B, tests) */
+/* A/B: a thin level is one of <= r rows (1..65535; 0 = the library's default,
+ * out[11] below) */
+#define SMFV_TRSM_THIN_ROWS(r) (((r) & 0xffff) << 8)
+/* out[0] levels, [1] rows of the widest level, [2] launches per execute,
+ * [3] chain launches, [4] rows solved by chain launches, [5] most levels in
+ * one chain launch, [6] strict entries used, [7] entries ignored (the other
+ * triangle; with UNIT_DIAG the diagonal too), [8] diagonal entries, [9] plan
+ * device bytes (0 from smfv_trsm_analyse), [10] analysis ms, [11] the
+ * thin-level threshold in rows */
+#define SMFV_TRSM_STATS 12
+SMFV_API int smfv_trsm_plan_create(smfv_trsm_plan_t *plan, int m, int64_t nnz, const int *h_row_ptr,
+                                   const int *h_col_idx, int K, int flags);
+SMFV_API int smfv_trsm_plan_bind_values(smfv_trsm_plan_t plan, const double *d_values, void *stream);
+SMFV_API int smfv_trsm_plan_execute(smfv_trsm_plan_t plan, const double *d_values, const double *d_X, int64_t ldx,
+                                    double *d_Y, int64_t ldy, void *stream);
+SMFV_API int smfv_trsm_plan_stats(smfv_trsm_plan_t plan, double out[SMFV_TRSM_STATS]);
+SMFV_API int smfv_trsm_plan_destroy(smfv_trsm_plan_t plan);
+/* Host only: the analysis of smfv_trsm_plan_create (levels, layout, schedule,
+ * verified by replay) and its figures, with the same refusals.  No device
+ * needed. */
+SMFV_API int smfv_trsm_analyse(int m, const int *h_row_ptr, const int *h_col_idx, int K, int flags,
+                               double out[SMFV_TRSM_STATS]);
+/* Host only: level[i] (1-based) of every row, order[p] the row at plan
+ * position p (rows by level, ascending row index inside a level) and the
+ * level count.  Only SMFV_TRSM_UPPER of `flags` matters (diagonal entries
+ * never set a level).  SMFV_ERR_INVALID for a column outside [0, m). */
+SMFV_API int smfv_trsm_levels(int m, const int *h_row_ptr, const int *h_col_idx, int flags, int *level, int *order,
+                              int *nlevels);
+
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,
  * `bytes` (multiple of 16, 16-B aligned pointers) by a 16-byte-per-lane
  * non-temporal copy kernel.  Read + write bytes / time = the measured

@@ -3,6 +3,7 @@ AlexisBalayre/SparseMatrixMultiplicationMPI).
 
     Y[m x K] = A_csr[m x n] * X[n x K]   (fp64)
     Y[n x K] = A_csr^T * X[m x K]        (transposed plans, spmm_t)
+    T Y = X, T a triangle of A_csr       (level-scheduled solves, sptrsm)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -27,6 +28,7 @@ from .inputs import (  # noqa: F401
 from .engine import (  # noqa: F401
     DeviceCSR,
     SpmmPlan,
+    TrsmPlan,
     VendorSpmm,
     Variant,
     compare,
@@ -37,6 +39,8 @@ from .engine import (  # noqa: F401
     sparseMatrixFatVectorMultiplyRowWise,
     spmm,
     spmm_t,
+    sptrsm,
+    trsm_analyse,
 )
 
 __version__ = "0.1.0"

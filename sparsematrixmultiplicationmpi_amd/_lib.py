@@ -70,6 +70,13 @@ _SIGS = {
     "smfv_plan_destroy": (c_int, [c_void_p]),
     "smfv_plan_is_transposed": (c_int, [c_void_p, _PI]),
     "smfv_csr_transpose": (c_int, [c_int, c_int, _PI, _PI, _PI, _PI, _PI]),
+    "smfv_trsm_plan_create": (c_int, [POINTER(c_void_p), c_int, c_int64, _PI, _PI, c_int, c_int]),
+    "smfv_trsm_plan_bind_values": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "smfv_trsm_plan_execute": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "smfv_trsm_plan_stats": (c_int, [c_void_p, _PD]),
+    "smfv_trsm_plan_destroy": (c_int, [c_void_p]),
+    "smfv_trsm_analyse": (c_int, [c_int, _PI, _PI, c_int, c_int, _PD]),
+    "smfv_trsm_levels": (c_int, [c_int, _PI, _PI, c_int, _PI, _PI, _PI]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_spmm_colpanel_f64": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

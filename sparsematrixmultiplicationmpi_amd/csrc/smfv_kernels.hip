@@ -23,6 +23,9 @@
 //            A's values into the transposed pattern's order; the sums run on
 //            the kernels above over that pattern
 //            <- SC/SparseMatrixFatVectorMultiply.cpp:17-27 on the CSR of A^T
+//   k_trsm_level, k_trsm_chain, k_trsm_diag   T Y = X (smfv_trsm_plan_*): a
+//            level of the solve across a grid, a run of thin levels in one
+//            block, the pivots of a bind; no counterpart in the reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -1647,6 +1650,218 @@ __global__ __launch_bounds__(256) void k_permute_vals(int64_t nnz, const int *__
     } else if (j < nnz) {
         tv[j] = va[(int64_t)__builtin_nontemporal_load(perm + j)];
     }
+}
+
+// ---------------------------------------------------------------------------
+// Triangular solve T Y = X (smfv_trsm_plan_*, include/smfv.h), level-scheduled
+// (smfv::TrsmPlan, smfv_plan.h).  Plan position p holds row order[p]; its
+// strict entries (column, bound value) stream contiguously from
+// ec / ev[ep[p] .. ep[p + 1]) in CSR order, its pivot is piv[p]:
+//   s = X[row]; s = fl(s - fl(v * Y[c])) per entry; Y[row] = fl(s / piv)
+// -- a separate multiply and subtract (contraction is off for this file) and
+// a true division.  A team of TEAM lanes covers the K columns, VEC doubles
+// per lane, as in k_rows; the (column, value) pairs of TEAM entries are read
+// by the team's lanes and broadcast by shuffle, up to 8 gathers in flight.
+// Y carries no __restrict__ and is read with ordinary loads: it may be X
+// itself (in place: an element is read and written by the same lane), and the
+// rows gathered were written by earlier launches or, in k_trsm_chain, by this
+// block before the last barrier.  No flags, no spinning, no atomics: a
+// dependency never crosses between workgroups inside a launch.
+// ---------------------------------------------------------------------------
+template <int VEC> __device__ __forceinline__ typename VecT<VEC>::T trsm_msub(typename VecT<VEC>::T s, double v, typename VecT<VEC>::T y)
+{
+    if constexpr (VEC == 1) {
+        const double p = v * y;
+        return s - p;
+    } else {
+        const double px = v * y.x, py = v * y.y;
+        return make_double2(s.x - px, s.y - py);
+    }
+}
+
+// A row in three steps, so that k_trsm_chain can run the first two for the
+// next level while this level is still being solved -- neither reads Y:
+//   trsm_fetch1  what is indexed by the plan position: the row, its entry
+//                range, its pivot;
+//   trsm_fetch2  what those name: the team's columns of X[row] and the
+//                (column, value) pairs of the row's first TEAM entries;
+//   trsm_finish  the gathers of Y, the arithmetic and the store.
+// X[row] may be read early also in place: no other row's lane writes it.
+template <int VEC> struct TrsmRow {
+    int row, js, je, myc;
+    double d, myv;
+    typename VecT<VEC>::T s0;
+};
+
+template <int VEC, bool UNIT>
+__device__ __forceinline__ void trsm_fetch1(TrsmRow<VEC> &q, int pos, const int *__restrict__ order,
+                                            const int *__restrict__ ep, const double *__restrict__ piv)
+{
+    q.row = order[pos];
+    q.js = ep[pos];
+    q.je = ep[pos + 1];
+    q.d = 1.0;
+    if constexpr (!UNIT) q.d = piv[pos];
+}
+
+template <int TEAM, int VEC>
+__device__ __forceinline__ void trsm_fetch2(TrsmRow<VEC> &q, int tl, const int *__restrict__ ec,
+                                            const double *__restrict__ ev, const double *X, int64_t ldx, int K)
+{
+    using V = VecT<VEC>;
+    q.s0 = V::zero();
+    if (tl * VEC < K) q.s0 = V::load(X + (int64_t)q.row * ldx + tl * VEC);
+    q.myc = 0;
+    q.myv = 0.0;
+    if (q.js + tl < q.je) {
+        q.myc = ec[q.js + tl];
+        q.myv = ev[q.js + tl];
+    }
+}
+
+template <int TEAM, int VEC, bool UNIT>
+__device__ __forceinline__ void trsm_finish(const TrsmRow<VEC> &q, int tl, const int *__restrict__ ec,
+                                            const double *__restrict__ ev, const double *X, int64_t ldx, int K, double *Y,
+                                            int64_t ldy)
+{
+    using V = VecT<VEC>;
+    constexpr int U = TEAM < 8 ? TEAM : 8;
+    const int js = q.js, je = q.je;
+    const int tbase = (threadIdx.x & 63) & ~(TEAM - 1);
+    const double *xrow = X + (int64_t)q.row * ldx;
+    double *yrow = Y + (int64_t)q.row * ldy;
+    const int npass = (K + TEAM * VEC - 1) / (TEAM * VEC);
+    for (int p = 0; p < npass; ++p) {
+        const int c = p * TEAM * VEC + tl * VEC;
+        const bool cok = c < K;
+        typename V::T s = q.s0;
+        if (p > 0) {
+            s = V::zero();
+            if (cok) s = V::load(xrow + c);
+        }
+        for (int j0 = js; j0 < je; j0 += TEAM) {
+            const int n = min(TEAM, je - j0);
+            int myc = q.myc;
+            double myv = q.myv;
+            if (j0 > js) {
+                myc = 0;
+                myv = 0.0;
+                if (tl < n) {
+                    myc = ec[j0 + tl];
+                    myv = ev[j0 + tl];
+                }
+            }
+            for (int t0 = 0; t0 < n; t0 += U) {
+                int cc[U];
+                double vv[U];
+                typename V::T y[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int src = tbase + min(t0 + u, TEAM - 1);
+                    cc[u] = __shfl(myc, src);
+                    vv[u] = __shfl(myv, src);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    y[u] = V::zero();
+                    if (cok && t0 + u < n) y[u] = V::load(Y + (int64_t)cc[u] * ldy + c);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (t0 + u < n) s = trsm_msub<VEC>(s, vv[u], y[u]);
+            }
+        }
+        if constexpr (!UNIT) {
+            if constexpr (VEC == 1) s = s / q.d;
+            else s = make_double2(s.x / q.d, s.y / q.d);
+        }
+        if (cok) V::store(yrow + c, s);
+    }
+}
+
+// One level across a grid: positions [pos_begin, pos_begin + nrows), a team
+// per row, 256 / TEAM rows per block.
+template <int TEAM, int VEC, bool UNIT>
+__global__ __launch_bounds__(256) void k_trsm_level(int pos_begin, int nrows, const int *__restrict__ order,
+                                                    const int *__restrict__ ep, const int *__restrict__ ec,
+                                                    const double *__restrict__ ev, const double *__restrict__ piv,
+                                                    const double *X, int64_t ldx, int K, double *Y, int64_t ldy)
+{
+    constexpr int RPB = 256 / TEAM;
+    const int64_t lrow = (int64_t)blockIdx.x * RPB + (int)(threadIdx.x / TEAM);
+    if (lrow >= nrows) return;  // whole team leaves together
+    const int tl = threadIdx.x & (TEAM - 1);
+    TrsmRow<VEC> q;
+    trsm_fetch1<VEC, UNIT>(q, pos_begin + (int)lrow, order, ep, piv);
+    trsm_fetch2<TEAM, VEC>(q, tl, ec, ev, X, ldx, K);
+    trsm_finish<TEAM, VEC, UNIT>(q, tl, ec, ev, X, ldx, K, Y, ldy);
+}
+
+// A run of thin levels [lev_begin, lev_end) in ONE 1024-lane block: the
+// block's 1024 / TEAM teams take a level's rows in passes (a level of any
+// width is covered), and a block barrier separates the levels: the stores of
+// a level are complete and visible to every wave of this block -- which all
+// read through this CU's L1 -- before the next level gathers them.  A level
+// of a few rows is all latency, so each team fetches its first row of the
+// NEXT level around the solve of this one (fetch1 before it, fetch2 after):
+// after the barrier only the gathers of Y, the arithmetic and the store are
+// left.  The grid is one block: launched wider, blocks past the first do
+// nothing.
+template <int TEAM, int VEC, bool UNIT>
+__global__ __launch_bounds__(1024) void k_trsm_chain(int lev_begin, int lev_end, const int *__restrict__ lp,
+                                                     const int *__restrict__ order, const int *__restrict__ ep,
+                                                     const int *__restrict__ ec, const double *__restrict__ ev,
+                                                     const double *__restrict__ piv, const double *X, int64_t ldx, int K,
+                                                     double *Y, int64_t ldy)
+{
+    constexpr int TEAMS = 1024 / TEAM;
+    if (blockIdx.x != 0) return;
+    const int team = (int)(threadIdx.x / TEAM), tl = threadIdx.x & (TEAM - 1);
+    int begin = lp[lev_begin], end = lp[lev_begin + 1];
+    TrsmRow<VEC> q = {};
+    bool have = begin + team < end;  // team-uniform
+    if (have) {
+        trsm_fetch1<VEC, UNIT>(q, begin + team, order, ep, piv);
+        trsm_fetch2<TEAM, VEC>(q, tl, ec, ev, X, ldx, K);
+    }
+    for (int l = lev_begin; l < lev_end; ++l) {
+        TrsmRow<VEC> nx = {};
+        int nend = end;
+        bool nhave = false;
+        if (l + 1 < lev_end) {
+            nend = lp[l + 2];
+            nhave = end + team < nend;
+            if (nhave) trsm_fetch1<VEC, UNIT>(nx, end + team, order, ep, piv);
+        }
+        if (have) trsm_finish<TEAM, VEC, UNIT>(q, tl, ec, ev, X, ldx, K, Y, ldy);
+        for (int pos = begin + team + TEAMS; pos < end; pos += TEAMS) {
+            TrsmRow<VEC> r;
+            trsm_fetch1<VEC, UNIT>(r, pos, order, ep, piv);
+            trsm_fetch2<TEAM, VEC>(r, tl, ec, ev, X, ldx, K);
+            trsm_finish<TEAM, VEC, UNIT>(r, tl, ec, ev, X, ldx, K, Y, ldy);
+        }
+        if (nhave) trsm_fetch2<TEAM, VEC>(nx, tl, ec, ev, X, ldx, K);
+        q = nx;
+        have = nhave;
+        begin = end;
+        end = nend;
+        __syncthreads();
+    }
+}
+
+// The pivots of a bind: piv[p] = the position's diagonal entries summed in
+// CSR order, d = va[first], then d = fl(d + va[next]).  One lane per position
+// (nearly every row has one diagonal entry).  The replay at create has shown
+// every position to have at least one.
+__global__ __launch_bounds__(256) void k_trsm_diag(int m, const int *__restrict__ dp, const int *__restrict__ ds,
+                                                   const double *__restrict__ va, double *__restrict__ piv)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= m) return;
+    const int s = dp[p], e = dp[p + 1];
+    double d = va[(int64_t)ds[s]];
+    for (int t = s + 1; t < e; ++t) d = d + va[(int64_t)ds[t]];
+    piv[p] = d;
 }
 // (r4) The cut rows of a NONZERO range (at most its first and last row):
 // row i's partial sum over its entries [s[i], e[i]), one block per row.
@@ -3691,6 +3906,210 @@ SMFV_API int smfv_fill_x_hash_f64(int64_t n, int K, uint64_t seed, double *d_X, 
     hipLaunchKernelGGL(k_fill_x_hash, dim3(4096), dim3(256), 0, as_stream(stream), n, K, seed, d_X,
                        ldx);
     SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Triangular solves (smfv_trsm_plan_*): the host plan (smfv::TrsmPlan) on the
+// device, the bound values and pivots, and the fixed launch sequence.
+// ---------------------------------------------------------------------------
+struct smfv_trsm_plan_s {
+    smfv::TrsmPlan hp;  // the schedule (launches, level pointers) and the figures
+    int *order = nullptr, *lev_ptr = nullptr, *ent_ptr = nullptr, *ent_col = nullptr, *ent_src = nullptr;
+    int *diag_ptr = nullptr, *diag_src = nullptr;
+    double *ent_val = nullptr, *piv = nullptr;  // written by every bind
+    size_t dev_bytes = 0;
+    double analysis_ms = 0.0;
+    hipEvent_t bind_ev = nullptr;
+    hipStream_t bind_stream = nullptr;
+    const double *bound_values = nullptr;
+    bool bound = false;
+    ~smfv_trsm_plan_s()
+    {
+        for (void *q : {(void *)order, (void *)lev_ptr, (void *)ent_ptr, (void *)ent_col, (void *)ent_src, (void *)diag_ptr,
+                        (void *)diag_src, (void *)ent_val, (void *)piv})
+            if (q) (void)hipFree(q);
+        if (bind_ev) (void)hipEventDestroy(bind_ev);
+    }
+};
+
+namespace {
+
+template <bool UNIT>
+int trsm_launch_level(const smfv_trsm_plan_s *p, const TrsmLaunch &L, int team, int vec, const double *X, int64_t ldx,
+                      double *Y, int64_t ldy, hipStream_t st)
+{
+    const int nrows = L.pos_end - L.pos_begin, rpb = 256 / team;
+    const unsigned nblk = (unsigned)((nrows + rpb - 1) / rpb);
+#define LV(T_, V_) hipLaunchKernelGGL((k_trsm_level<T_, V_, UNIT>), dim3(nblk), dim3(256), 0, st, L.pos_begin, nrows, \
+                                      p->order, p->ent_ptr, p->ent_col, p->ent_val, p->piv, X, ldx, p->hp.K, Y, ldy)
+    SMFV_TEAM_SWITCH(team, vec, LV)
+#undef LV
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+template <bool UNIT>
+int trsm_launch_chain(const smfv_trsm_plan_s *p, const TrsmLaunch &L, int team, int vec, const double *X, int64_t ldx,
+                      double *Y, int64_t ldy, hipStream_t st)
+{
+#define LC(T_, V_) hipLaunchKernelGGL((k_trsm_chain<T_, V_, UNIT>), dim3(1), dim3(TRSM_CHAIN_LANES), 0, st, L.lev_begin, \
+                                      L.lev_end, p->lev_ptr, p->order, p->ent_ptr, p->ent_col, p->ent_val, p->piv, X, ldx, \
+                                      p->hp.K, Y, ldy)
+    SMFV_TEAM_SWITCH(team, vec, LC)
+#undef LC
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+int trsm_host_plan(int m, const int *rp, const int *ci, int K, int flags, TrsmPlan &hp)
+{
+    std::string err;
+    if (!build_trsm_plan(m, rp, ci, K, flags, hp, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+SMFV_API int smfv_trsm_levels(int m, const int *h_row_ptr, const int *h_col_idx, int flags, int *level, int *order,
+                              int *nlevels)
+{
+    std::string err;
+    if (!trsm_levels(m, h_row_ptr, h_col_idx, flags, level, order, nlevels, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_analyse(int m, const int *h_row_ptr, const int *h_col_idx, int K, int flags,
+                               double out[SMFV_TRSM_STATS])
+{
+    SMFV_REQUIRE(out, "null argument");
+    const auto t_start = std::chrono::steady_clock::now();
+    TrsmPlan hp;
+    const int rc = trsm_host_plan(m, h_row_ptr, h_col_idx, K, flags, hp);
+    if (rc) return rc;
+    hp.stats(out);
+    out[10] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_plan_create(smfv_trsm_plan_t *out, int m, int64_t nnz, const int *h_row_ptr, const int *h_col_idx,
+                                   int K, int flags)
+{
+    SMFV_REQUIRE(out, "null plan pointer");
+    SMFV_REQUIRE(m >= 0 && nnz >= 0 && nnz <= 0x7fffffff, "bad sizes");
+    SMFV_REQUIRE(h_row_ptr && h_row_ptr[0] == 0 && h_row_ptr[m] == nnz, "row_ptr missing, row_ptr[0] != 0 or row_ptr[m] != nnz");
+    const auto t_start = std::chrono::steady_clock::now();
+    auto *p = new smfv_trsm_plan_s;
+    // the pattern, the diagonal and the schedule are checked on the host
+    // before the first device call
+    int rc = trsm_host_plan(m, h_row_ptr, h_col_idx, K, flags, p->hp);
+    const TrsmPlan &hp = p->hp;
+    if (!rc) rc = upload(&p->order, hp.order, p->dev_bytes);
+    if (!rc) rc = upload(&p->lev_ptr, hp.lev_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->ent_ptr, hp.ent_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->ent_col, hp.ent_col, p->dev_bytes);
+    if (!rc) rc = upload(&p->ent_src, hp.ent_src, p->dev_bytes);
+    if (!rc && !(flags & SMFV_TRSM_UNIT_DIAG)) {
+        rc = upload(&p->diag_ptr, hp.diag_ptr, p->dev_bytes);
+        if (!rc) rc = upload(&p->diag_src, hp.diag_src, p->dev_bytes);
+    }
+    if (!rc) {
+        const size_t bv = std::max<size_t>((size_t)hp.strict, 1) * sizeof(double);
+        const size_t bp = std::max<size_t>((size_t)m, 1) * sizeof(double);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->ent_val), bv);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->piv), bp);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&p->bind_ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            set_error("trsm plan: device allocation failed: %s", hipGetErrorString(e));
+            rc = SMFV_ERR_HIP;
+        } else {
+            p->dev_bytes += bv + bp;
+        }
+    }
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    p->analysis_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    *out = p;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_plan_bind_values(smfv_trsm_plan_t plan, const double *d_values, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    const TrsmPlan &hp = plan->hp;
+    SMFV_REQUIRE(d_values || hp.strict + hp.diag == 0, "null values");
+    hipStream_t st = as_stream(stream);
+    if (hp.strict > 0) {  // A's values into plan order: the gather of the transposed plans
+        hipLaunchKernelGGL(k_permute_vals, dim3((unsigned)((hp.strict + 511) / 512)), dim3(256), 0, st, hp.strict,
+                           plan->ent_src, d_values, plan->ent_val);
+        SMFV_LAUNCHED();
+    }
+    if (hp.m > 0 && !(hp.flags & SMFV_TRSM_UNIT_DIAG)) {
+        hipLaunchKernelGGL(k_trsm_diag, dim3((unsigned)((hp.m + 255) / 256)), dim3(256), 0, st, hp.m, plan->diag_ptr,
+                           plan->diag_src, d_values, plan->piv);
+        SMFV_LAUNCHED();
+    }
+    SMFV_HIP(hipEventRecord(plan->bind_ev, st));
+    plan->bind_stream = st;
+    plan->bound_values = d_values;
+    plan->bound = true;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_plan_execute(smfv_trsm_plan_t plan, const double *d_values, const double *d_X, int64_t ldx,
+                                    double *d_Y, int64_t ldy, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    const TrsmPlan &hp = plan->hp;
+    SMFV_REQUIRE(ldx >= hp.K && ldy >= hp.K, "leading dimension smaller than K");
+    if (!plan->bound || d_values != plan->bound_values) {
+        set_error("trsm plan: values not bound (call smfv_trsm_plan_bind_values with these d_values)");
+        return SMFV_ERR_INVALID;
+    }
+    if (hp.m == 0) return SMFV_OK;
+    SMFV_REQUIRE(d_X && d_Y, "null X / Y");
+    hipStream_t st = as_stream(stream);
+    int rc = order_after_bind(st, plan->bind_stream, plan->bind_ev, "trsm plan: the bound values and pivots");
+    if (rc) return rc;
+    const int vec = pick_vec(d_X, ldx, d_Y, ldy, hp.K);
+    const int team = pick_team(hp.K, vec);
+    const bool unit = (hp.flags & SMFV_TRSM_UNIT_DIAG) != 0;
+    for (const TrsmLaunch &L : hp.launches) {
+        if (L.chain)
+            rc = unit ? trsm_launch_chain<true>(plan, L, team, vec, d_X, ldx, d_Y, ldy, st)
+                      : trsm_launch_chain<false>(plan, L, team, vec, d_X, ldx, d_Y, ldy, st);
+        else
+            rc = unit ? trsm_launch_level<true>(plan, L, team, vec, d_X, ldx, d_Y, ldy, st)
+                      : trsm_launch_level<false>(plan, L, team, vec, d_X, ldx, d_Y, ldy, st);
+        if (rc) return rc;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_plan_stats(smfv_trsm_plan_t plan, double out[SMFV_TRSM_STATS])
+{
+    SMFV_REQUIRE(plan && out, "null argument");
+    plan->hp.stats(out);
+    out[9] = (double)plan->dev_bytes;
+    out[10] = plan->analysis_ms;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_trsm_plan_destroy(smfv_trsm_plan_t plan)
+{
+    delete plan;
     return SMFV_OK;
 }
 

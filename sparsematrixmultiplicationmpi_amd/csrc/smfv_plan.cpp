@@ -1702,4 +1702,219 @@ bool csr_transpose(int m, int n, const int *rp, const int *ci, int *t_rp, int *t
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Triangular solve: levels, layout, schedule (smfv_plan.h).
+// ---------------------------------------------------------------------------
+namespace {
+
+bool trsm_fail(std::string *err, const char *fmt, long long a, long long b)
+{
+    if (err) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, fmt, a, b);
+        *err = buf;
+    }
+    return false;
+}
+
+// row_ptr and every column index, before anything is indexed by one
+bool trsm_validate(int m, const int *rp, const int *ci, std::string *err)
+{
+    if (m < 0) return trsm_fail(err, "trsm: bad size m = %lld (%lld)", m, 0);
+    if (!rp) return trsm_fail(err, "trsm: null row_ptr (m = %lld, %lld)", m, 0);
+    if (rp[0] != 0) return trsm_fail(err, "trsm: row_ptr[0] = %lld, not %lld", rp[0], 0);
+    for (int r = 0; r < m; ++r)
+        if (rp[r + 1] < rp[r]) return trsm_fail(err, "trsm: row_ptr decreases at row %lld (%lld)", r, rp[r + 1]);
+    const int64_t nnz = rp[m];
+    if (nnz > 0 && !ci) return trsm_fail(err, "trsm: null col_idx (m = %lld, nnz = %lld)", m, nnz);
+    for (int r = 0; r < m; ++r)
+        for (int64_t j = rp[r]; j < rp[r + 1]; ++j)
+            if (ci[j] < 0 || ci[j] >= m)
+                return trsm_fail(err, "trsm: column index %lld outside [0, %lld)", ci[j], m);
+    return true;
+}
+
+// the sweep, on a validated pattern: level[] (1-based) and the level count
+int trsm_sweep(int m, const int *rp, const int *ci, bool upper, int *level)
+{
+    int nlev = 0;
+    for (int t = 0; t < m; ++t) {
+        const int i = upper ? m - 1 - t : t;
+        int l = 0;
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+            const int c = ci[j];
+            if (upper ? c > i : c < i) l = std::max(l, level[c]);
+        }
+        level[i] = l + 1;
+        nlev = std::max(nlev, l + 1);
+    }
+    return nlev;
+}
+
+// rows by level, ascending row index inside a level; lev_ptr: nlev + 1 entries
+void trsm_order(int m, int nlev, const int *level, int *order, std::vector<int> &lev_ptr)
+{
+    lev_ptr.assign((size_t)nlev + 1, 0);
+    for (int i = 0; i < m; ++i) ++lev_ptr[(size_t)level[i]];
+    for (int l = 0; l < nlev; ++l) lev_ptr[(size_t)l + 1] += lev_ptr[(size_t)l];
+    std::vector<int> next(lev_ptr.begin(), lev_ptr.end() - 1);
+    for (int i = 0; i < m; ++i) order[next[(size_t)level[i] - 1]++] = i;
+}
+
+}  // namespace
+
+bool trsm_levels(int m, const int *rp, const int *ci, int flags, int *level, int *order, int *nlevels, std::string *err)
+{
+    if (!trsm_validate(m, rp, ci, err)) return false;
+    if (m > 0 && (!level || !order)) return trsm_fail(err, "trsm: null level / order (m = %lld, %lld)", m, 0);
+    const int nlev = trsm_sweep(m, rp, ci, (flags & TRSM_UPPER) != 0, level);
+    std::vector<int> lev_ptr;
+    trsm_order(m, nlev, level, order, lev_ptr);
+    if (nlevels) *nlevels = nlev;
+    return true;
+}
+
+void TrsmPlan::stats(double out[TRSM_NSTATS]) const
+{
+    for (int i = 0; i < TRSM_NSTATS; ++i) out[i] = 0.0;
+    out[0] = nlevels;
+    out[1] = widest;
+    out[2] = (double)launches.size();
+    out[3] = chain_launches;
+    out[4] = (double)chain_rows;
+    out[5] = chain_max_levels;
+    out[6] = (double)strict;
+    out[7] = (double)ignored;
+    out[8] = (double)diag;
+    out[11] = thin;
+}
+
+bool build_trsm_plan(int m, const int *rp, const int *ci, int K, int flags, TrsmPlan &P, std::string *err)
+{
+    if (flags & ~TRSM_FLAGS) return trsm_fail(err, "trsm: unknown flags %lld (known: %lld)", flags, TRSM_FLAGS);
+    if ((flags & TRSM_NO_CHAIN) && (flags & TRSM_CHAIN_ALL))
+        return trsm_fail(err, "trsm: SMFV_TRSM_NO_CHAIN and SMFV_TRSM_CHAIN_ALL exclude each other (%lld, %lld)", flags, 0);
+    if (K < 1) return trsm_fail(err, "trsm: K = %lld, must be >= %lld", K, 1);
+    if (!trsm_validate(m, rp, ci, err)) return false;
+    const bool upper = (flags & TRSM_UPPER) != 0, unit = (flags & TRSM_UNIT_DIAG) != 0;
+    const int64_t nnz = rp[m];
+    if (!unit)
+        for (int i = 0; i < m; ++i) {
+            bool has = false;
+            for (int64_t j = rp[i]; j < rp[i + 1] && !has; ++j) has = ci[j] == i;
+            if (!has) return trsm_fail(err, "trsm: row %lld has no diagonal entry (m = %lld; SMFV_TRSM_UNIT_DIAG solves without one)", i, m);
+        }
+    P = TrsmPlan();
+    P.m = m;
+    P.K = K;
+    P.flags = flags;
+    const int asked = (flags >> TRSM_THIN_SHIFT) & TRSM_THIN_MASK;
+    P.thin = asked ? asked : TRSM_THIN_DEFAULT;
+    P.level.assign((size_t)m, 0);
+    P.order.assign((size_t)m, 0);
+    P.nlevels = trsm_sweep(m, rp, ci, upper, P.level.data());
+    trsm_order(m, P.nlevels, P.level.data(), P.order.data(), P.lev_ptr);
+    for (int l = 0; l < P.nlevels; ++l) P.widest = std::max(P.widest, P.lev_ptr[(size_t)l + 1] - P.lev_ptr[(size_t)l]);
+
+    // layout: each position's strict entries, then its diagonal entries, in CSR order
+    P.ent_ptr.assign((size_t)m + 1, 0);
+    if (!unit) P.diag_ptr.assign((size_t)m + 1, 0);
+    for (int p = 0; p < m; ++p) {
+        const int i = P.order[(size_t)p];
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+            const int c = ci[j];
+            if (upper ? c > i : c < i) {
+                P.ent_col.push_back(c);
+                P.ent_src.push_back((int)j);
+            } else if (c == i && !unit) {
+                P.diag_src.push_back((int)j);
+            } else {
+                ++P.ignored;
+            }
+        }
+        P.ent_ptr[(size_t)p + 1] = (int)P.ent_col.size();
+        if (!unit) P.diag_ptr[(size_t)p + 1] = (int)P.diag_src.size();
+    }
+    P.strict = (int64_t)P.ent_col.size();
+    P.diag = (int64_t)P.diag_src.size();
+
+    // schedule
+    auto width = [&](int l) { return P.lev_ptr[(size_t)l + 1] - P.lev_ptr[(size_t)l]; };
+    auto is_thin = [&](int l) {
+        if (flags & TRSM_NO_CHAIN) return false;
+        if (flags & TRSM_CHAIN_ALL) return true;
+        return width(l) <= P.thin;
+    };
+    for (int l = 0; l < P.nlevels;) {
+        int e = l + 1;
+        const bool chain = is_thin(l);
+        if (chain)
+            while (e < P.nlevels && is_thin(e)) ++e;
+        P.launches.push_back({chain ? 1 : 0, l, e, P.lev_ptr[(size_t)l], P.lev_ptr[(size_t)e]});
+        if (chain) {
+            ++P.chain_launches;
+            P.chain_rows += P.lev_ptr[(size_t)e] - P.lev_ptr[(size_t)l];
+            P.chain_max_levels = std::max(P.chain_max_levels, e - l);
+        }
+        l = e;
+    }
+
+    // replay.  where[i]: the launch and level that solve row i; a strict
+    // entry's row must lie in an earlier launch, or in the same chain launch
+    // at an earlier level
+    std::vector<int> launch_of((size_t)m, -1), pos_of((size_t)m, -1);
+    int next_pos = 0, next_lev = 0;
+    for (size_t q = 0; q < P.launches.size(); ++q) {
+        const TrsmLaunch &L = P.launches[q];
+        if (L.lev_begin != next_lev || L.lev_end <= L.lev_begin || L.lev_end > P.nlevels || L.pos_begin != next_pos ||
+            L.pos_begin != P.lev_ptr[(size_t)L.lev_begin] || L.pos_end != P.lev_ptr[(size_t)L.lev_end] ||
+            (!L.chain && L.lev_end != L.lev_begin + 1))
+            return trsm_fail(err, "trsm: replay: launch %lld does not continue the schedule (level %lld)", (long long)q, L.lev_begin);
+        for (int p = L.pos_begin; p < L.pos_end; ++p) {
+            const int i = P.order[(size_t)p];
+            if (i < 0 || i >= m || launch_of[(size_t)i] >= 0) return trsm_fail(err, "trsm: replay: position %lld schedules row %lld twice or out of range", p, i);
+            launch_of[(size_t)i] = (int)q;
+            pos_of[(size_t)i] = p;
+        }
+        next_pos = L.pos_end;
+        next_lev = L.lev_end;
+    }
+    if (next_pos != m || next_lev != P.nlevels) return trsm_fail(err, "trsm: replay: schedule ends at position %lld of %lld", next_pos, m);
+    int64_t used = 0;
+    for (int p = 0; p < m; ++p) {
+        const int i = P.order[(size_t)p];
+        if (p > 0 && P.level[(size_t)P.order[(size_t)p - 1]] == P.level[(size_t)i] && P.order[(size_t)p - 1] >= i)
+            return trsm_fail(err, "trsm: replay: level of row %lld is not in row order (position %lld)", i, p);
+        if (p < P.lev_ptr[(size_t)P.level[(size_t)i] - 1] || p >= P.lev_ptr[(size_t)P.level[(size_t)i]])
+            return trsm_fail(err, "trsm: replay: row %lld lies outside its level (position %lld)", i, p);
+        int64_t j = rp[i];  // the row's entries again, in CSR order, against the layout
+        int e = P.ent_ptr[(size_t)p], d = unit ? 0 : P.diag_ptr[(size_t)p];
+        for (; j < rp[i + 1]; ++j) {
+            const int c = ci[j];
+            if (upper ? c > i : c < i) {
+                if (e >= P.ent_ptr[(size_t)p + 1] || P.ent_col[(size_t)e] != c || P.ent_src[(size_t)e] != j)
+                    return trsm_fail(err, "trsm: replay: strict entry %lld of row %lld is misplaced", (long long)j, i);
+                const bool earlier = launch_of[(size_t)c] < launch_of[(size_t)i] ||
+                                     (launch_of[(size_t)c] == launch_of[(size_t)i] && P.launches[(size_t)launch_of[(size_t)i]].chain &&
+                                      P.level[(size_t)c] < P.level[(size_t)i]);
+                if (!earlier) return trsm_fail(err, "trsm: replay: row %lld is scheduled no later than row %lld, which it needs", c, i);
+                ++e;
+                ++used;
+            } else if (c == i && !unit) {
+                if (d >= P.diag_ptr[(size_t)p + 1] || P.diag_src[(size_t)d] != j)
+                    return trsm_fail(err, "trsm: replay: diagonal entry %lld of row %lld is misplaced", (long long)j, i);
+                ++d;
+                ++used;
+            } else {
+                ++used;
+            }
+        }
+        if (e != P.ent_ptr[(size_t)p + 1] || (!unit && (d != P.diag_ptr[(size_t)p + 1] || d == P.diag_ptr[(size_t)p])))
+            return trsm_fail(err, "trsm: replay: row %lld keeps entries the pattern does not have (position %lld)", i, p);
+    }
+    if (used != nnz || P.strict + P.diag + P.ignored != nnz)
+        return trsm_fail(err, "trsm: replay: %lld entries accounted for, of %lld", (long long)used, (long long)nnz);
+    return true;
+}
+
 }  // namespace smfv

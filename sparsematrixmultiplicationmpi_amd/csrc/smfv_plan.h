@@ -338,4 +338,68 @@ bool build_spmv_chunks(int m, int n, const int *row_ptr, const int *col_idx, int
 bool csr_transpose(int m, int n, const int *row_ptr, const int *col_idx, int *t_row_ptr, int *t_col_idx,
                    int *t_perm, std::string *err);
 
+// ---------------------------------------------------------------------------
+// Level schedule of a sparse triangular solve T Y = X (smfv_trsm_plan_*,
+// include/smfv.h): T the lower (or, with TRSM_UPPER, the upper) triangle of a
+// square CSR pattern; entries of the other triangle are ignored, and with
+// TRSM_UNIT_DIAG so are the diagonal entries.  level[i] = 1 + the highest
+// level among the rows that row i's strict entries name (1: no strict entry),
+// in one O(nnz) sweep in substitution order.  Rows are laid out by level, in
+// ascending row index inside a level (a stable counting sort), and plan
+// position p holds row order[p].  Each row's strict entries sit contiguously,
+// in CSR order, at ent_ptr[p] .. ent_ptr[p + 1]: the column (a row of Y) and
+// the index of the value in A's arrays (the slot of the bound value has the
+// same index in the plan's device values).  The diagonal entries of position
+// p are diag_src[diag_ptr[p] .. diag_ptr[p + 1]), in CSR order.
+//
+// Schedule: a level of more than `thin` rows is WIDE and is one grid launch
+// (k_trsm_level); a maximal run of consecutive levels of <= thin rows each is
+// one CHAIN launch (k_trsm_chain: one 1024-lane block that walks the levels
+// with a block barrier between them).  Dependencies therefore cross between
+// workgroups only at kernel boundaries.  TRSM_NO_CHAIN: every level a grid
+// launch; TRSM_CHAIN_ALL: all levels in one chain launch.
+// ---------------------------------------------------------------------------
+constexpr int TRSM_UPPER = 1, TRSM_UNIT_DIAG = 2, TRSM_NO_CHAIN = 4, TRSM_CHAIN_ALL = 8;
+constexpr int TRSM_THIN_SHIFT = 8, TRSM_THIN_MASK = 0xffff;  // SMFV_TRSM_THIN_ROWS(r)
+constexpr int TRSM_FLAGS = 15 | (TRSM_THIN_MASK << TRSM_THIN_SHIFT);
+constexpr int TRSM_THIN_DEFAULT = 64;  // rows; profiles/trsm/README.md
+constexpr int TRSM_CHAIN_LANES = 1024;
+constexpr int TRSM_NSTATS = 12;
+
+struct TrsmLaunch {
+    int chain;               // 1: k_trsm_chain over levels [lev_begin, lev_end); 0: k_trsm_level of one level
+    int lev_begin, lev_end;  // 0-based levels
+    int pos_begin, pos_end;  // plan positions
+};
+
+struct TrsmPlan {
+    int m = 0, K = 0, flags = 0, nlevels = 0, widest = 0, thin = 0;
+    std::vector<int> level;     // per row, 1-based
+    std::vector<int> order;     // per plan position: its row
+    std::vector<int> lev_ptr;   // nlevels + 1: first position of each level
+    std::vector<int> ent_ptr;   // m + 1: per position, its strict entries
+    std::vector<int> ent_col;   // per strict entry: the row of Y it reads
+    std::vector<int> ent_src;   // per strict entry: its index in A's values
+    std::vector<int> diag_ptr;  // m + 1 (empty with TRSM_UNIT_DIAG)
+    std::vector<int> diag_src;  // per diagonal entry: its index in A's values
+    std::vector<TrsmLaunch> launches;
+    int64_t strict = 0, ignored = 0, diag = 0, chain_rows = 0;
+    int chain_launches = 0, chain_max_levels = 0;
+    // smfv_trsm_analyse's out[] but [9] device bytes and [10] analysis ms
+    void stats(double out[TRSM_NSTATS]) const;
+};
+
+// Validates the pattern (row_ptr, every column in [0, m)) and writes level[m],
+// order[m] and *nlevels.  false (with *err) on a bad input.
+bool trsm_levels(int m, const int *row_ptr, const int *col_idx, int flags, int *level, int *order, int *nlevels,
+                 std::string *err);
+// The plan above, verified by replay before it is returned: every row in
+// exactly one launch, every strict dependency in an earlier launch or in an
+// earlier level of the same chain launch, every entry of the pattern
+// accounted for (strict + diagonal + ignored = nnz), sources inside the
+// row.  false (with *err): a bad pattern or bad flags, K < 1, a row with no
+// diagonal entry (without TRSM_UNIT_DIAG; the first such row is named), or a
+// failed replay.
+bool build_trsm_plan(int m, const int *row_ptr, const int *col_idx, int K, int flags, TrsmPlan &out, std::string *err);
+
 }  // namespace smfv

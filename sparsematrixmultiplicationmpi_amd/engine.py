@@ -90,6 +90,19 @@ class DeviceCSR:
             p.bind_values(stream)  # values changed since the bind: snapshot them again
         return p
 
+    def trsm_plan(self, K: int, uplo: str = "lower", unit_diag: bool = False, chain: str = "auto",
+                  stream: torch.cuda.Stream | None = None) -> "TrsmPlan":
+        """The cached triangular-solve plan of (K, uplo, unit_diag, chain),
+        created (and bound on `stream`) on first use and bound again when
+        `values` has changed since its bind."""
+        key = ("trsm", int(K), uplo, bool(unit_diag), chain)
+        p = self._plans.get(key)
+        if p is None:
+            p = self._plans[key] = TrsmPlan(self, K, uplo, unit_diag, chain, stream=stream)
+        elif p.bound_version != self.values_version():
+            p.bind_values(stream)
+        return p
+
     def values_version(self) -> tuple[int, int]:
         """(address, torch version counter) of `values`: changes with every
         in-place write torch performs and with a new tensor."""
@@ -290,6 +303,102 @@ def spmm_t(variant: int, A: DeviceCSR, X: torch.Tensor, Y: torch.Tensor | None =
     if Y is None:
         Y = torch.empty((A.n, K), dtype=torch.float64, device=A.device)
     return A.plan(variant, K, stream, transpose=True).run(X, Y, stream)
+
+
+TRSM_UPPER, TRSM_UNIT_DIAG, TRSM_NO_CHAIN, TRSM_CHAIN_ALL = 1, 2, 4, 8  # SMFV_TRSM_*
+TRSM_STATS = 12  # SMFV_TRSM_STATS
+TRSM_STAT_NAMES = ("levels", "widest_level", "launches", "chain_launches", "chain_rows", "chain_max_levels",
+                   "strict_entries", "ignored_entries", "diag_entries", "plan_bytes", "analysis_ms", "thin_rows")
+
+
+def trsm_flags(uplo: str = "lower", unit_diag: bool = False, chain: str = "auto", thin_rows: int = 0) -> int:
+    """The SMFV_TRSM_* flags of a solve (ValueError for an unknown setting)."""
+    if uplo not in ("lower", "upper"):
+        raise ValueError(f"uplo must be 'lower' or 'upper', got {uplo!r}")
+    if chain not in ("auto", "off", "all"):
+        raise ValueError(f"chain must be 'auto', 'off' or 'all', got {chain!r}")
+    if not 0 <= int(thin_rows) <= 0xffff:
+        raise ValueError("thin_rows must be in [0, 65535]")
+    return ((TRSM_UPPER if uplo == "upper" else 0) | (TRSM_UNIT_DIAG if unit_diag else 0)
+            | {"auto": 0, "off": TRSM_NO_CHAIN, "all": TRSM_CHAIN_ALL}[chain] | (int(thin_rows) << 8))
+
+
+def _trsm_stats(out) -> dict:
+    return {k: (float(out[i]) if k == "analysis_ms" else int(out[i])) for i, k in enumerate(TRSM_STAT_NAMES)}
+
+
+def trsm_analyse(A: SparseMatrix, K: int, uplo: str = "lower", unit_diag: bool = False, chain: str = "auto",
+                 thin_rows: int = 0) -> dict:
+    """The figures of a solve's host analysis (smfv_trsm_analyse; no device)."""
+    ip = ctypes.POINTER(ctypes.c_int)
+    rp = np.ascontiguousarray(A.rowPtr, dtype=np.int32)
+    ci = np.ascontiguousarray(A.colIndices, dtype=np.int32)
+    out = (ctypes.c_double * TRSM_STATS)()
+    call("smfv_trsm_analyse", A.numRows, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), K,
+         trsm_flags(uplo, unit_diag, chain, thin_rows), out)
+    return _trsm_stats(out)
+
+
+class TrsmPlan:
+    """A triangular solve T Y = X analysed once for (pattern of A, K): T the
+    lower (uplo="upper": the upper) triangle of the square A, the other
+    triangle ignored, X and Y m x K (include/smfv.h, smfv_trsm_plan_*).  The
+    result is bit-identical to sequential substitution in CSR order.
+    unit_diag: the diagonal entries are ignored too and taken as 1.
+    chain: "auto" runs each run of thin levels in one launch of a single block
+    and each wide level as a grid launch; "off" / "all" force one launch per
+    level / one launch in all (A/B, tests); thin_rows sets the threshold (A/B).
+    The plan computes from its own copy of the values, written by
+    bind_values(): bind again after A.values change."""
+
+    def __init__(self, A: DeviceCSR, K: int, uplo: str = "lower", unit_diag: bool = False, chain: str = "auto",
+                 stream: torch.cuda.Stream | None = None, thin_rows: int = 0):
+        flags = trsm_flags(uplo, unit_diag, chain, thin_rows)
+        if A.m != A.n:
+            raise ValueError(f"a triangular solve needs a square matrix, got {A.m} x {A.n}")
+        self.A, self.K, self.uplo, self.unit_diag, self.chain = A, int(K), uplo, bool(unit_diag), chain
+        self._plan = ctypes.c_void_p()
+        ip = ctypes.POINTER(ctypes.c_int)
+        call("smfv_trsm_plan_create", byref(self._plan), A.m, A.nnz, A.h_row_ptr.ctypes.data_as(ip),
+             A.h_col_idx.ctypes.data_as(ip), self.K, flags)
+        self.bind_values(stream)
+
+    def bind_values(self, stream: torch.cuda.Stream | None = None) -> None:
+        """(Re)bind the plan to A's current device values: the values into plan order, and the pivots."""
+        call("smfv_trsm_plan_bind_values", self._plan, self.A.values.data_ptr(), stream_handle(stream))
+        self.bound_version = self.A.values_version()
+
+    def stats(self) -> dict:
+        out = (ctypes.c_double * TRSM_STATS)()
+        call("smfv_trsm_plan_stats", self._plan, out)
+        return _trsm_stats(out)
+
+    def solve(self, X: torch.Tensor, Y: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """Y = T^-1 X (asynchronous on `stream`); Y may be X itself (in place)."""
+        A, K = self.A, self.K
+        if Y is None:
+            Y = torch.empty((A.m, K), dtype=torch.float64, device=A.device)
+        ldx = _check_dense(X, A.m, K, "X")
+        ldy = _check_dense(Y, A.m, K, "Y")
+        call("smfv_trsm_plan_execute", self._plan, A.values.data_ptr(), X.data_ptr(), ldx, Y.data_ptr(), ldy,
+             stream_handle(stream))
+        return Y
+
+    def __del__(self):
+        try:
+            if self._plan:
+                call("smfv_trsm_plan_destroy", self._plan)
+                self._plan = ctypes.c_void_p()
+        except Exception:
+            pass
+
+
+def sptrsm(A: DeviceCSR, X: torch.Tensor, uplo: str = "lower", unit_diag: bool = False,
+           Y: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Y = T^-1 X on the device, T the lower / upper triangle of A, through
+    A's cached solve plan for (K, uplo, unit_diag)."""
+    return A.trsm_plan(X.shape[1], uplo, unit_diag, stream=stream).solve(X, Y, stream)
 
 
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,
