@@ -538,6 +538,94 @@ SMFV_API int smfv_trsm_analyse(int m, const int *h_row_ptr, const int *h_col_idx
 SMFV_API int smfv_trsm_levels(int m, const int *h_row_ptr, const int *h_col_idx, int flags, int *level, int *order,
                               int *nlevels);
 
+/* ---- ILU(0): the factors the triangular solves above apply ----------------
+ * Input: a square m x m CSR pattern (row_ptr, col_idx, int32) and fp64 values
+ * a in CSR order.  Output: f, nnz doubles in the same CSR order; the
+ * strict-lower entries of f are L (unit diagonal, not stored), the diagonal
+ * and strict-upper entries are U.  No atomics, a fixed launch sequence.
+ *
+ * Semantics.
+ *     for i = 0 .. m-1:
+ *         w[j] = a[j] for every CSR entry j of row i
+ *         for every strict-lower entry p of row i, in ASCENDING COLUMN
+ *                                   k = col_idx[p] (not in CSR order):
+ *             w[p] = fl(w[p] / f[diag(k)])      a true IEEE division, never a
+ *                                               reciprocal multiply
+ *             for every entry q of row k with col_idx[q] > k:
+ *                 if row i has an entry r with col_idx[r] == col_idx[q]:
+ *                     w[r] = fl(w[r] - fl(w[p] * f[q]))   separate multiply
+ *                                               and subtract, never an FMA
+ *         f[j] = w[j] for every entry j of row i
+ * Row k is final before row i uses it; entries of row k outside row i's
+ * pattern are dropped (zero fill-in).  Each w[r] is updated once per step k,
+ * in ascending k, and the order of the q inside a step does not touch the
+ * arithmetic, so the result is a function of the input alone: it is
+ * bit-identical to this loop, NaN for NaN and the sign of zero included, on
+ * every run and with every schedule setting below.
+ *   - Unsorted rows are legal: the elimination order is by column, the
+ *     output stays in the caller's CSR order.
+ *   - A zero or non-finite pivot gives what IEEE gives (+-inf, NaN), written
+ *     without any check, read-back or synchronisation.
+ *   - In place: d_F == d_values is allowed (row i is read before it is
+ *     written, and other rows read only earlier rows of f); any other overlap
+ *     is undefined.
+ *   - The result plugs into the solves above: a trsm plan of f's pattern with
+ *     SMFV_TRSM_UNIT_DIAG (lower: L, f's diagonal ignored), then one with
+ *     SMFV_TRSM_UPPER (U, exactly one diagonal entry per row), apply
+ *     U^-1 L^-1.
+ *   - Out of scope: IC(0), ILU(k) and threshold variants, pivot shifting or
+ *     repair, distributed plans, the C++ drop-in, the CLI, bench.py.
+ *
+ * Refused at create with SMFV_ERR_INVALID and a message, before any device
+ * allocation: a row with no diagonal entry (the message names the first such
+ * row), a column repeated inside a row (ILU(0) of a pattern with duplicates
+ * has no agreed meaning; the message names row and column), a column index
+ * outside [0, m), a row_ptr that does not start at 0 or decreases, unknown
+ * flag bits, NO_CHAIN together with CHAIN_ALL, an update list of 2^31 pairs
+ * or more.
+ *
+ * Execution.  Row i needs exactly the rows its strict-lower
+ * entries name, so the levels, the order of the rows and the schedule are
+ * those of the lower solve (smfv_trsm_levels with flags = 0): a level of more
+ * than `thin` rows is one grid launch (k_ilu0_level, a wavefront per row, its
+ * working values in a slot of 256 doubles of LDS: 8,192 bytes per 256-lane
+ * block), a maximal run of consecutive thinner levels one launch of a single
+ * 1024-lane block with a block barrier between levels (k_ilu0_chain, 32,768
+ * bytes of LDS).  A row of more than 256 entries is a LONG row and is
+ * eliminated by a whole block, in d_F itself, with a block barrier between
+ * its steps; rows of any length work.  A dependency crosses between
+ * workgroups only at a kernel boundary: no flags, no spinning, no atomics, no
+ * cooperative launch.
+ *
+ * Streams: create allocates device memory and synchronises.  factor is
+ * asynchronous and graph-capturable -- no allocation, no synchronisation, no
+ * host read-back -- and reads d_values when it runs: the plan holds no values
+ * and has no bind.  The pattern must not change over a plan's life.  A plan
+ * is not thread-safe. */
+typedef struct smfv_ilu0_plan_s *smfv_ilu0_plan_t;
+#define SMFV_ILU0_NO_CHAIN 4   /* every level its own launch (A/B, tests) */
+#define SMFV_ILU0_CHAIN_ALL 8  /* all levels in the one-block kernel, one launch (A/B, tests) */
+/* A/B: a thin level is one of <= r rows (1..65535; 0 = the library's default,
+ * out[14] below) */
+#define SMFV_ILU0_THIN_ROWS(r) (((r) & 0xffff) << 8)
+/* out[0] levels, [1] rows of the widest level, [2] launches per
+ * factorisation, [3] chain launches, [4] rows in chain launches, [5] most
+ * levels in one chain launch, [6] steps (strict-lower entries), [7] update
+ * pairs, [8] most steps in a row, [9] most pairs in a row, [10] long rows,
+ * [11] LDS slot entries, [12] plan device bytes (0 from smfv_ilu0_analyse),
+ * [13] analysis ms, [14] the thin-level threshold in rows */
+#define SMFV_ILU0_STATS 15
+SMFV_API int smfv_ilu0_plan_create(smfv_ilu0_plan_t *plan, int m, int64_t nnz, const int *h_row_ptr,
+                                   const int *h_col_idx, int flags);
+SMFV_API int smfv_ilu0_plan_factor(smfv_ilu0_plan_t plan, const double *d_values, double *d_F, void *stream);
+SMFV_API int smfv_ilu0_plan_stats(smfv_ilu0_plan_t plan, double out[SMFV_ILU0_STATS]);
+SMFV_API int smfv_ilu0_plan_destroy(smfv_ilu0_plan_t plan);
+/* Host only: the analysis of smfv_ilu0_plan_create (levels, symbolic phase,
+ * schedule, verified by replay) and its figures, with the same refusals.  No
+ * device needed. */
+SMFV_API int smfv_ilu0_analyse(int m, const int *h_row_ptr, const int *h_col_idx, int flags,
+                               double out[SMFV_ILU0_STATS]);
+
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,
  * `bytes` (multiple of 16, 16-B aligned pointers) by a 16-byte-per-lane
  * non-temporal copy kernel.  Read + write bytes / time = the measured

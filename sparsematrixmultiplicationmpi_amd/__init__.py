@@ -4,6 +4,7 @@ AlexisBalayre/SparseMatrixMultiplicationMPI).
     Y[m x K] = A_csr[m x n] * X[n x K]   (fp64)
     Y[n x K] = A_csr^T * X[m x K]        (transposed plans, spmm_t)
     T Y = X, T a triangle of A_csr       (level-scheduled solves, sptrsm)
+    L U ~ A_csr on A's pattern           (ILU(0), ilu0 / Ilu0Preconditioner)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -27,11 +28,15 @@ from .inputs import (  # noqa: F401
 )
 from .engine import (  # noqa: F401
     DeviceCSR,
+    Ilu0Plan,
+    Ilu0Preconditioner,
     SpmmPlan,
     TrsmPlan,
     VendorSpmm,
     Variant,
     compare,
+    ilu0,
+    ilu0_analyse,
     fill_x_hash,
     sparseMatrixFatVectorMultiply,
     sparseMatrixFatVectorMultiplyColumnWise,

@@ -77,6 +77,11 @@ _SIGS = {
     "smfv_trsm_plan_destroy": (c_int, [c_void_p]),
     "smfv_trsm_analyse": (c_int, [c_int, _PI, _PI, c_int, c_int, _PD]),
     "smfv_trsm_levels": (c_int, [c_int, _PI, _PI, c_int, _PI, _PI, _PI]),
+    "smfv_ilu0_plan_create": (c_int, [POINTER(c_void_p), c_int, c_int64, _PI, _PI, c_int]),
+    "smfv_ilu0_plan_factor": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "smfv_ilu0_plan_stats": (c_int, [c_void_p, _PD]),
+    "smfv_ilu0_plan_destroy": (c_int, [c_void_p]),
+    "smfv_ilu0_analyse": (c_int, [c_int, _PI, _PI, c_int, _PD]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_spmm_colpanel_f64": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

@@ -26,6 +26,8 @@
 //   k_trsm_level, k_trsm_chain, k_trsm_diag   T Y = X (smfv_trsm_plan_*): a
 //            level of the solve across a grid, a run of thin levels in one
 //            block, the pivots of a bind; no counterpart in the reference
+//   k_ilu0_level, k_ilu0_chain   ILU(0) of A's values (smfv_ilu0_plan_*), on
+//            the lower solve's schedule; no counterpart in the reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -4108,6 +4110,307 @@ SMFV_API int smfv_trsm_plan_stats(smfv_trsm_plan_t plan, double out[SMFV_TRSM_ST
 }
 
 SMFV_API int smfv_trsm_plan_destroy(smfv_trsm_plan_t plan)
+{
+    delete plan;
+    return SMFV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// ILU(0) (smfv_ilu0_plan_*, include/smfv.h), level-scheduled like the solves
+// above (smfv::Ilu0Plan, smfv_plan.h).  A row is eliminated by a GROUP of NL
+// lanes -- a wavefront (WAVE: the row's working values w in the wave's LDS
+// slot, loaded from `va`, stored to F at the end) or, for a long row, a whole
+// block (w is the row's place in F itself).  Steps run in sequence; in each,
+// every lane reads w[p] and the pivot and forms the same quotient q (a true
+// division), the lanes stride over the step's pairs, w[t] = fl(w[t] - fl(q *
+// F[src])) (contraction is off for this file), and the group synchronises:
+// targets are distinct inside a step, so no two lanes touch one slot, and a
+// pair never targets a step's own entry.  Lane 0 stores q to w[p] only after
+// that synchronisation, when every lane has read w[p]; no later step reads it.
+// For a long row that store goes to F after the step's __syncthreads(): in
+// k_ilu0_chain the barrier that ends the level completes it before any wave
+// reads the row; in k_ilu0_level nothing follows it but the end of the kernel,
+// which makes it visible to the next launch -- no row of the same launch
+// reads this one.
+// What a step reads of the plan and of earlier rows of F does not depend on
+// this row, so it is fetched for four steps at a time, ahead of their
+// arithmetic: the entry, the pivot and each lane's first pair.
+// A wavefront orders its LDS hand-off with a wavefront-scope fence and a wave
+// barrier, a block with __syncthreads() (its waves share this CU's L1, the
+// argument k_trsm_chain rests on).  F carries no __restrict__ and is read with
+// ordinary loads: it may be `va` itself, and the rows read were written by
+// earlier launches or, in k_ilu0_chain, by this block before the last barrier.
+// No flags, no spinning, no atomics.
+// ---------------------------------------------------------------------------
+namespace smfv {
+
+template <bool WAVE> __device__ __forceinline__ void ilu0_sync()
+{
+    if constexpr (WAVE) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+template <bool WAVE, int NL>
+__device__ __forceinline__ void ilu0_row(double *w, int ln, int rs, int len, int sb, int se, const int *__restrict__ sent,
+                                         const int *__restrict__ sdiag, const int *__restrict__ pp,
+                                         const int *__restrict__ ptgt, const int *__restrict__ psrc, const double *va,
+                                         double *F)
+{
+    constexpr int U = 4;  // steps fetched ahead together
+    if constexpr (WAVE) {
+        for (int j = ln; j < len; j += NL) w[j] = va[(int64_t)rs + j];
+    } else if (va != F) {  // w is F + rs
+        for (int j = ln; j < len; j += NL) w[j] = va[(int64_t)rs + j];
+    }
+    ilu0_sync<WAVE>();
+    for (int s0 = sb; s0 < se; s0 += U) {
+        // what U steps read of the plan and of earlier rows of F (final since
+        // an earlier launch or barrier): entry, pivot, and this lane's first
+        // pair of each step -- all issued before the first step's arithmetic
+        int p[U], te[U], t1[U], tg[U];
+        double d[U], fv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = min(s0 + u, se - 1);
+            p[u] = sent[s];
+            d[u] = F[(int64_t)sdiag[s]];
+            t1[u] = pp[s] + ln;
+            te[u] = pp[s + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            tg[u] = 0;
+            fv[u] = 0.0;
+            if (t1[u] < te[u]) {
+                tg[u] = ptgt[t1[u]];
+                fv[u] = F[(int64_t)psrc[t1[u]]];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (s0 + u < se) {  // group-uniform
+                const double q = w[p[u]] / d[u];
+                if (t1[u] < te[u]) {
+                    const double prod = q * fv[u];
+                    w[tg[u]] = w[tg[u]] - prod;
+                }
+                for (int t = t1[u] + NL; t < te[u]; t += NL) {
+                    const int tgt = ptgt[t];
+                    const double prod = q * F[(int64_t)psrc[t]];
+                    w[tgt] = w[tgt] - prod;
+                }
+                ilu0_sync<WAVE>();
+                if (ln == 0) w[p[u]] = q;
+            }
+        }
+    }
+    if constexpr (WAVE) {
+        ilu0_sync<WAVE>();
+        for (int j = ln; j < len; j += NL) F[(int64_t)rs + j] = w[j];
+    }
+}
+
+// One level across a grid: positions [pos_begin, pos_begin + nrows).  Blocks
+// [0, nshort) take four positions each, a wavefront per row, and leave the
+// long rows out; block nshort + t takes the level's t-th long row whole.
+__global__ __launch_bounds__(256) void k_ilu0_level(int pos_begin, int nrows, int nshort, int long_begin,
+                                                    const int *__restrict__ rb, const int *__restrict__ rl,
+                                                    const int *__restrict__ sp, const int *__restrict__ sent,
+                                                    const int *__restrict__ sdiag, const int *__restrict__ pp,
+                                                    const int *__restrict__ ptgt, const int *__restrict__ psrc,
+                                                    const int *__restrict__ lpos, const double *va, double *F)
+{
+    __shared__ double slot[4][ILU0_SLOT];
+    if ((int)blockIdx.x < nshort) {
+        const int wv = threadIdx.x >> 6, lrow = (int)blockIdx.x * 4 + wv;
+        if (lrow >= nrows) return;  // whole wavefront; no block barrier on this side
+        const int pos = pos_begin + lrow, len = rl[pos];
+        if (len > ILU0_SLOT) return;
+        ilu0_row<true, 64>(slot[wv], threadIdx.x & 63, rb[pos], len, sp[pos], sp[pos + 1], sent, sdiag, pp, ptgt, psrc, va, F);
+    } else {
+        const int pos = lpos[long_begin + ((int)blockIdx.x - nshort)];
+        const int rs = rb[pos];
+        ilu0_row<false, 256>(F + rs, threadIdx.x, rs, rl[pos], sp[pos], sp[pos + 1], sent, sdiag, pp, ptgt, psrc, va, F);
+    }
+}
+
+// A run of thin levels [lev_begin, lev_end) in ONE 1024-lane block: its 16
+// wavefronts take a level's rows 16 at a time, then the block eliminates the
+// level's long rows one after the other (every wave runs the same number of
+// barriers), and a block barrier separates the levels: a row's stores to F
+// are complete and visible to every wave of this block before the next level
+// reads them.  The grid is one block.
+__global__ __launch_bounds__(1024) void k_ilu0_chain(int lev_begin, int lev_end, const int *__restrict__ lp,
+                                                     const int *__restrict__ llp, const int *__restrict__ rb,
+                                                     const int *__restrict__ rl, const int *__restrict__ sp,
+                                                     const int *__restrict__ sent, const int *__restrict__ sdiag,
+                                                     const int *__restrict__ pp, const int *__restrict__ ptgt,
+                                                     const int *__restrict__ psrc, const int *__restrict__ lpos,
+                                                     const double *va, double *F)
+{
+    __shared__ double slot[ILU0_CHAIN_LANES / 64][ILU0_SLOT];
+    if (blockIdx.x != 0) return;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int l = lev_begin; l < lev_end; ++l) {
+        const int begin = lp[l], end = lp[l + 1];
+        for (int pos = begin + wv; pos < end; pos += ILU0_CHAIN_LANES / 64) {
+            const int len = rl[pos];
+            if (len <= ILU0_SLOT)
+                ilu0_row<true, 64>(slot[wv], lane, rb[pos], len, sp[pos], sp[pos + 1], sent, sdiag, pp, ptgt, psrc, va, F);
+        }
+        const int lb = llp[l], le = llp[l + 1];  // block-uniform
+        for (int t = lb; t < le; ++t) {
+            const int pos = lpos[t];
+            const int rs = rb[pos];
+            ilu0_row<false, ILU0_CHAIN_LANES>(F + rs, threadIdx.x, rs, rl[pos], sp[pos], sp[pos + 1], sent, sdiag, pp, ptgt,
+                                              psrc, va, F);
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace smfv
+
+// ---------------------------------------------------------------------------
+// ILU(0) plans (smfv_ilu0_plan_*): the host plan (smfv::Ilu0Plan) on the
+// device and the fixed launch sequence.  No values are held: no bind.
+// ---------------------------------------------------------------------------
+struct smfv_ilu0_plan_s {
+    smfv::Ilu0Plan hp;  // after create: the schedule (launches, long_ptr) and the figures; the lists are freed
+    int *lev_ptr = nullptr, *long_ptr = nullptr, *long_pos = nullptr, *row_beg = nullptr, *row_len = nullptr;
+    int *step_ptr = nullptr, *step_ent = nullptr, *step_diag = nullptr, *pair_ptr = nullptr, *pair_tgt = nullptr;
+    int *pair_src = nullptr;
+    size_t dev_bytes = 0;
+    double analysis_ms = 0.0;
+    ~smfv_ilu0_plan_s()
+    {
+        for (void *q : {(void *)lev_ptr, (void *)long_ptr, (void *)long_pos, (void *)row_beg, (void *)row_len, (void *)step_ptr,
+                        (void *)step_ent, (void *)step_diag, (void *)pair_ptr, (void *)pair_tgt, (void *)pair_src})
+            if (q) (void)hipFree(q);
+    }
+};
+
+namespace {
+
+int ilu0_host_plan(int m, const int *rp, const int *ci, int flags, Ilu0Plan &hp)
+{
+    std::string err;
+    if (!build_ilu0_plan(m, rp, ci, flags, hp, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+int ilu0_launch(const smfv_ilu0_plan_s *p, const TrsmLaunch &L, const double *va, double *F, hipStream_t st)
+{
+    if (L.chain) {
+        hipLaunchKernelGGL(k_ilu0_chain, dim3(1), dim3(ILU0_CHAIN_LANES), 0, st, L.lev_begin, L.lev_end, p->lev_ptr,
+                           p->long_ptr, p->row_beg, p->row_len, p->step_ptr, p->step_ent, p->step_diag, p->pair_ptr,
+                           p->pair_tgt, p->pair_src, p->long_pos, va, F);
+    } else {
+        const int nrows = L.pos_end - L.pos_begin, nshort = (nrows + 3) / 4;
+        const int lb = p->hp.long_ptr[(size_t)L.lev_begin], nlong = p->hp.long_ptr[(size_t)L.lev_begin + 1] - lb;
+        hipLaunchKernelGGL(k_ilu0_level, dim3((unsigned)(nshort + nlong)), dim3(256), 0, st, L.pos_begin, nrows, nshort, lb,
+                           p->row_beg, p->row_len, p->step_ptr, p->step_ent, p->step_diag, p->pair_ptr, p->pair_tgt,
+                           p->pair_src, p->long_pos, va, F);
+    }
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+SMFV_API int smfv_ilu0_analyse(int m, const int *h_row_ptr, const int *h_col_idx, int flags, double out[SMFV_ILU0_STATS])
+{
+    SMFV_REQUIRE(out, "null argument");
+    const auto t_start = std::chrono::steady_clock::now();
+    Ilu0Plan hp;
+    const int rc = ilu0_host_plan(m, h_row_ptr, h_col_idx, flags, hp);
+    if (rc) return rc;
+    hp.stats(out);
+    out[13] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_ilu0_plan_create(smfv_ilu0_plan_t *out, int m, int64_t nnz, const int *h_row_ptr, const int *h_col_idx,
+                                   int flags)
+{
+    SMFV_REQUIRE(out, "null plan pointer");
+    SMFV_REQUIRE(m >= 0 && nnz >= 0 && nnz <= 0x7fffffff, "bad sizes");
+    SMFV_REQUIRE(h_row_ptr, "null row_ptr");
+    const auto t_start = std::chrono::steady_clock::now();
+    auto *p = new smfv_ilu0_plan_s;
+    // the pattern, the diagonal, the duplicates and the schedule are checked
+    // on the host before the first device call
+    int rc = ilu0_host_plan(m, h_row_ptr, h_col_idx, flags, p->hp);
+    if (!rc && h_row_ptr[m] != nnz) {
+        set_error("ilu0: row_ptr[m] = %d, not nnz = %lld", h_row_ptr[m], (long long)nnz);
+        rc = SMFV_ERR_INVALID;
+    }
+    const Ilu0Plan &hp = p->hp;
+    if (!rc) rc = upload(&p->lev_ptr, hp.lev_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->long_ptr, hp.long_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->long_pos, hp.long_pos, p->dev_bytes);
+    if (!rc) rc = upload(&p->row_beg, hp.row_beg, p->dev_bytes);
+    if (!rc) rc = upload(&p->row_len, hp.row_len, p->dev_bytes);
+    if (!rc) rc = upload(&p->step_ptr, hp.step_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->step_ent, hp.step_ent, p->dev_bytes);
+    if (!rc) rc = upload(&p->step_diag, hp.step_diag, p->dev_bytes);
+    if (!rc) rc = upload(&p->pair_ptr, hp.pair_ptr, p->dev_bytes);
+    if (!rc) rc = upload(&p->pair_tgt, hp.pair_tgt, p->dev_bytes);
+    if (!rc) rc = upload(&p->pair_src, hp.pair_src, p->dev_bytes);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    {
+        // the lists now live on the device; factor and stats read only m, the
+        // launches, long_ptr and the counts, so the host copies go
+        // (tens of MB: 8 bytes per pair)
+        Ilu0Plan &h = p->hp;
+        for (std::vector<int> *v : {&h.level, &h.order, &h.lev_ptr, &h.row_beg, &h.row_len, &h.step_ptr, &h.step_ent,
+                                    &h.step_diag, &h.pair_ptr, &h.pair_tgt, &h.pair_src, &h.long_pos})
+            std::vector<int>().swap(*v);
+    }
+    p->analysis_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    *out = p;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_ilu0_plan_factor(smfv_ilu0_plan_t plan, const double *d_values, double *d_F, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    const Ilu0Plan &hp = plan->hp;
+    if (hp.m == 0) return SMFV_OK;
+    SMFV_REQUIRE(d_values && d_F, "null values / F");
+    hipStream_t st = as_stream(stream);
+    for (const TrsmLaunch &L : hp.launches) {
+        const int rc = ilu0_launch(plan, L, d_values, d_F, st);
+        if (rc) return rc;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_ilu0_plan_stats(smfv_ilu0_plan_t plan, double out[SMFV_ILU0_STATS])
+{
+    SMFV_REQUIRE(plan && out, "null argument");
+    plan->hp.stats(out);
+    out[12] = (double)plan->dev_bytes;
+    out[13] = plan->analysis_ms;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_ilu0_plan_destroy(smfv_ilu0_plan_t plan)
 {
     delete plan;
     return SMFV_OK;

@@ -1917,4 +1917,225 @@ bool build_trsm_plan(int m, const int *rp, const int *ci, int K, int flags, Trsm
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// ILU(0): symbolic phase and schedule (smfv_plan.h).
+// ---------------------------------------------------------------------------
+void Ilu0Plan::stats(double out[ILU0_NSTATS]) const
+{
+    for (int i = 0; i < ILU0_NSTATS; ++i) out[i] = 0.0;
+    out[0] = nlevels;
+    out[1] = widest;
+    out[2] = (double)launches.size();
+    out[3] = chain_launches;
+    out[4] = (double)chain_rows;
+    out[5] = chain_max_levels;
+    out[6] = (double)steps;
+    out[7] = (double)pairs;
+    out[8] = max_steps;
+    out[9] = (double)max_pairs;
+    out[10] = long_rows;
+    out[11] = ILU0_SLOT;
+    out[14] = thin;
+}
+
+bool build_ilu0_plan(int m, const int *rp, const int *ci, int flags, Ilu0Plan &P, std::string *err)
+{
+    if (flags & ~ILU0_FLAGS) return trsm_fail(err, "ilu0: unknown flags %lld (known: %lld)", flags, ILU0_FLAGS);
+    if ((flags & ILU0_NO_CHAIN) && (flags & ILU0_CHAIN_ALL))
+        return trsm_fail(err, "ilu0: SMFV_ILU0_NO_CHAIN and SMFV_ILU0_CHAIN_ALL exclude each other (%lld, %lld)", flags, 0);
+    {
+        std::string e;
+        if (!trsm_validate(m, rp, ci, &e)) {
+            if (err) *err = "ilu0" + e.substr(4);  // the shared pattern check, under this family's name
+            return false;
+        }
+    }
+    // one diagonal entry per row and no column twice in a row; diag[i]: its CSR index
+    std::vector<int> diag((size_t)m, -1), seen((size_t)m, -1);
+    for (int i = 0; i < m; ++i) {
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+            const int c = ci[j];
+            if (seen[(size_t)c] == i) return trsm_fail(err, "ilu0: row %lld holds column %lld more than once", i, c);
+            seen[(size_t)c] = i;
+            if (c == i) diag[(size_t)i] = (int)j;
+        }
+        if (diag[(size_t)i] < 0) return trsm_fail(err, "ilu0: row %lld has no diagonal entry (m = %lld)", i, m);
+    }
+    // an upper bound of the pair count first (every step at most row k's length),
+    // the exact count only where the bound does not settle it
+    const int64_t LIMIT = (int64_t)1 << 31;
+    auto count_pairs = [&](bool exact) {
+        std::vector<int> mark(exact ? (size_t)m : 0, -1);
+        int64_t n = 0;
+        for (int i = 0; i < m; ++i) {
+            if (exact)
+                for (int64_t j = rp[i]; j < rp[i + 1]; ++j) mark[(size_t)ci[j]] = i;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+                const int k = ci[j];
+                if (k >= i) continue;
+                if (!exact) {
+                    n += rp[k + 1] - rp[k];
+                    continue;
+                }
+                for (int64_t q = rp[k]; q < rp[k + 1]; ++q) n += ci[q] > k && mark[(size_t)ci[q]] == i;
+            }
+        }
+        return n;
+    };
+    if (count_pairs(false) >= LIMIT) {
+        const int64_t n = count_pairs(true);
+        if (n >= LIMIT) return trsm_fail(err, "ilu0: %lld update pairs, the plan holds fewer than %lld", (long long)n, (long long)LIMIT);
+    }
+
+    P = Ilu0Plan();
+    P.m = m;
+    P.flags = flags;
+    const int asked = (flags >> ILU0_THIN_SHIFT) & ILU0_THIN_MASK;
+    P.thin = asked ? asked : ILU0_THIN_DEFAULT;
+    P.level.assign((size_t)m, 0);
+    P.order.assign((size_t)m, 0);
+    P.nlevels = trsm_sweep(m, rp, ci, false, P.level.data());
+    trsm_order(m, P.nlevels, P.level.data(), P.order.data(), P.lev_ptr);
+    for (int l = 0; l < P.nlevels; ++l) P.widest = std::max(P.widest, P.lev_ptr[(size_t)l + 1] - P.lev_ptr[(size_t)l]);
+
+    // symbolic phase.  where[c]: the index inside row i of its entry in column
+    // c, valid while stamp[c] == i
+    std::vector<int> where((size_t)m, 0), stamp((size_t)m, -1);
+    std::vector<std::pair<int, int>> lower;  // (column, index inside the row)
+    P.row_beg.assign((size_t)m, 0);
+    P.row_len.assign((size_t)m, 0);
+    P.step_ptr.assign((size_t)m + 1, 0);
+    P.pair_ptr.assign(1, 0);
+    P.long_ptr.assign((size_t)P.nlevels + 1, 0);
+    for (int p = 0; p < m; ++p) {
+        const int i = P.order[(size_t)p];
+        const int rs = rp[i], len = rp[i + 1] - rp[i];
+        P.row_beg[(size_t)p] = rs;
+        P.row_len[(size_t)p] = len;
+        if (len > ILU0_SLOT) {
+            P.long_pos.push_back(p);
+            ++P.long_ptr[(size_t)P.level[(size_t)i]];
+        }
+        lower.clear();
+        for (int t = 0; t < len; ++t) {
+            const int c = ci[(size_t)rs + t];
+            stamp[(size_t)c] = i;
+            where[(size_t)c] = t;
+            if (c < i) lower.push_back({c, t});
+        }
+        std::sort(lower.begin(), lower.end());
+        int64_t row_pairs = 0;
+        for (const auto &kt : lower) {
+            const int k = kt.first;
+            P.step_ent.push_back(kt.second);
+            P.step_diag.push_back(diag[(size_t)k]);
+            for (int64_t q = rp[k]; q < rp[k + 1]; ++q) {
+                const int c = ci[q];
+                if (c > k && stamp[(size_t)c] == i) {
+                    P.pair_tgt.push_back(where[(size_t)c]);
+                    P.pair_src.push_back((int)q);
+                }
+            }
+            row_pairs += (int64_t)P.pair_tgt.size() - P.pair_ptr.back();
+            P.pair_ptr.push_back((int)P.pair_tgt.size());
+        }
+        P.step_ptr[(size_t)p + 1] = (int)P.step_ent.size();
+        P.max_steps = std::max(P.max_steps, (int)lower.size());
+        P.max_pairs = std::max(P.max_pairs, row_pairs);
+    }
+    for (int l = 0; l < P.nlevels; ++l) P.long_ptr[(size_t)l + 1] += P.long_ptr[(size_t)l];
+    P.steps = (int64_t)P.step_ent.size();
+    P.pairs = (int64_t)P.pair_tgt.size();
+    P.long_rows = (int)P.long_pos.size();
+
+    // schedule: build_trsm_plan's rule
+    auto width = [&](int l) { return P.lev_ptr[(size_t)l + 1] - P.lev_ptr[(size_t)l]; };
+    auto is_thin = [&](int l) {
+        if (flags & ILU0_NO_CHAIN) return false;
+        if (flags & ILU0_CHAIN_ALL) return true;
+        return width(l) <= P.thin;
+    };
+    for (int l = 0; l < P.nlevels;) {
+        int e = l + 1;
+        const bool chain = is_thin(l);
+        if (chain)
+            while (e < P.nlevels && is_thin(e)) ++e;
+        P.launches.push_back({chain ? 1 : 0, l, e, P.lev_ptr[(size_t)l], P.lev_ptr[(size_t)e]});
+        if (chain) {
+            ++P.chain_launches;
+            P.chain_rows += P.lev_ptr[(size_t)e] - P.lev_ptr[(size_t)l];
+            P.chain_max_levels = std::max(P.chain_max_levels, e - l);
+        }
+        l = e;
+    }
+
+    // replay
+    std::vector<int> launch_of((size_t)m, -1);
+    int next_pos = 0, next_lev = 0;
+    for (size_t q = 0; q < P.launches.size(); ++q) {
+        const TrsmLaunch &L = P.launches[q];
+        if (L.lev_begin != next_lev || L.lev_end <= L.lev_begin || L.lev_end > P.nlevels || L.pos_begin != next_pos ||
+            L.pos_begin != P.lev_ptr[(size_t)L.lev_begin] || L.pos_end != P.lev_ptr[(size_t)L.lev_end] ||
+            (!L.chain && L.lev_end != L.lev_begin + 1))
+            return trsm_fail(err, "ilu0: replay: launch %lld does not continue the schedule (level %lld)", (long long)q, L.lev_begin);
+        for (int p = L.pos_begin; p < L.pos_end; ++p) {
+            const int i = P.order[(size_t)p];
+            if (i < 0 || i >= m || launch_of[(size_t)i] >= 0) return trsm_fail(err, "ilu0: replay: position %lld schedules row %lld twice or out of range", p, i);
+            launch_of[(size_t)i] = (int)q;
+        }
+        next_pos = L.pos_end;
+        next_lev = L.lev_end;
+    }
+    if (next_pos != m || next_lev != P.nlevels) return trsm_fail(err, "ilu0: replay: schedule ends at position %lld of %lld", next_pos, m);
+    int64_t recount = 0;
+    size_t nlong = 0;
+    std::vector<int> cols;  // row i's columns, sorted: the recount looks columns up here, not in the stamp map
+    for (int p = 0; p < m; ++p) {
+        const int i = P.order[(size_t)p];
+        const int rs = rp[i], len = rp[i + 1] - rp[i];
+        const int lv = P.level[(size_t)i];
+        if (p < P.lev_ptr[(size_t)lv - 1] || p >= P.lev_ptr[(size_t)lv])
+            return trsm_fail(err, "ilu0: replay: row %lld lies outside its level (position %lld)", i, p);
+        if (P.row_beg[(size_t)p] != rs || P.row_len[(size_t)p] != len)
+            return trsm_fail(err, "ilu0: replay: position %lld does not hold row %lld's entry range", p, i);
+        if (len > ILU0_SLOT) {
+            if (nlong >= P.long_pos.size() || P.long_pos[nlong] != p || (int)nlong < P.long_ptr[(size_t)lv - 1] ||
+                (int)nlong >= P.long_ptr[(size_t)lv])
+                return trsm_fail(err, "ilu0: replay: long row %lld is not listed with its level (position %lld)", i, p);
+            ++nlong;
+        }
+        cols.assign(ci + rs, ci + rs + len);
+        std::sort(cols.begin(), cols.end());
+        int nlower = 0;
+        for (int t = 0; t < len; ++t) nlower += ci[(size_t)rs + t] < i;
+        if (P.step_ptr[(size_t)p + 1] - P.step_ptr[(size_t)p] != nlower)
+            return trsm_fail(err, "ilu0: replay: row %lld has %lld steps", i, P.step_ptr[(size_t)p + 1] - P.step_ptr[(size_t)p]);
+        int prev = -1;
+        for (int s = P.step_ptr[(size_t)p]; s < P.step_ptr[(size_t)p + 1]; ++s) {
+            const int t = P.step_ent[(size_t)s];
+            if (t < 0 || t >= len) return trsm_fail(err, "ilu0: replay: a step of row %lld leaves the row (%lld)", i, t);
+            const int k = ci[(size_t)rs + t];
+            if (k >= i || k <= prev) return trsm_fail(err, "ilu0: replay: the steps of row %lld do not ascend (column %lld)", i, k);
+            prev = k;
+            const int d = P.step_diag[(size_t)s];
+            if (d < rp[k] || d >= rp[k + 1] || ci[(size_t)d] != k)
+                return trsm_fail(err, "ilu0: replay: step (%lld, %lld) misses the pivot", i, k);
+            const bool earlier = launch_of[(size_t)k] < launch_of[(size_t)i] ||
+                                 (launch_of[(size_t)k] == launch_of[(size_t)i] && P.launches[(size_t)launch_of[(size_t)i]].chain &&
+                                  P.level[(size_t)k] < lv);
+            if (!earlier) return trsm_fail(err, "ilu0: replay: row %lld is scheduled no later than row %lld, which it needs", k, i);
+            for (int u = P.pair_ptr[(size_t)s]; u < P.pair_ptr[(size_t)s + 1]; ++u) {
+                const int tg = P.pair_tgt[(size_t)u], sr = P.pair_src[(size_t)u];
+                if (tg < 0 || tg >= len || sr < rp[k] || sr >= rp[k + 1] || ci[(size_t)sr] <= k || ci[(size_t)sr] != ci[(size_t)rs + tg])
+                    return trsm_fail(err, "ilu0: replay: a pair of step (%lld, %lld) is misplaced", i, k);
+            }
+            for (int64_t q = rp[k]; q < rp[k + 1]; ++q)
+                recount += ci[q] > k && std::binary_search(cols.begin(), cols.end(), ci[q]);
+        }
+    }
+    if (nlong != P.long_pos.size() || recount != P.pairs || (int64_t)P.pair_ptr.size() != P.steps + 1 || P.pair_ptr.back() != P.pairs)
+        return trsm_fail(err, "ilu0: replay: %lld update pairs recounted, the plan holds %lld", (long long)recount, (long long)P.pairs);
+    return true;
+}
+
 }  // namespace smfv

@@ -402,4 +402,61 @@ bool trsm_levels(int m, const int *row_ptr, const int *col_idx, int flags, int *
 // failed replay.
 bool build_trsm_plan(int m, const int *row_ptr, const int *col_idx, int K, int flags, TrsmPlan &out, std::string *err);
 
+// ---------------------------------------------------------------------------
+// ILU(0) of a square CSR pattern (smfv_ilu0_plan_*, include/smfv.h): the
+// symbolic phase and the level schedule.  Row i needs exactly the rows its
+// strict-lower entries name, so the levels, the order and the WIDE / CHAIN
+// schedule are those of the lower solve above (same sweep, same `thin` rule).
+// Per plan position p: the row's entry range in A's CSR (row_beg, row_len) and
+// its steps step_ptr[p] .. step_ptr[p + 1], one per strict-lower entry (i, k)
+// in ASCENDING COLUMN k: step_ent, the entry's index inside the row, and
+// step_diag, the CSR index of k's diagonal entry.  Per step its update pairs
+// pair_ptr[s] .. pair_ptr[s + 1]: pair_tgt, the index inside row i of the
+// entry updated, and pair_src, the CSR index of the entry of row k (right of
+// k) with the same column.  Entries of row k that row i lacks give no pair
+// (zero fill-in).  A row of more than ILU0_SLOT entries is LONG: the kernels
+// give it a whole block instead of a wavefront; long_pos lists the positions
+// of the long rows in ascending order and long_ptr[l] .. long_ptr[l + 1] are
+// those of level l.
+// ---------------------------------------------------------------------------
+constexpr int ILU0_NO_CHAIN = 4, ILU0_CHAIN_ALL = 8;
+constexpr int ILU0_THIN_SHIFT = 8, ILU0_THIN_MASK = 0xffff;  // SMFV_ILU0_THIN_ROWS(r)
+constexpr int ILU0_FLAGS = 12 | (ILU0_THIN_MASK << ILU0_THIN_SHIFT);
+constexpr int ILU0_THIN_DEFAULT = TRSM_THIN_DEFAULT;  // profiles/ilu0/README.md
+constexpr int ILU0_SLOT = 256;                        // entries of a wavefront's LDS slot
+constexpr int ILU0_CHAIN_LANES = 1024;
+constexpr int ILU0_NSTATS = 15;
+
+struct Ilu0Plan {
+    int m = 0, flags = 0, nlevels = 0, widest = 0, thin = 0;
+    std::vector<int> level;      // per row, 1-based
+    std::vector<int> order;      // per plan position: its row
+    std::vector<int> lev_ptr;    // nlevels + 1: first position of each level
+    std::vector<int> row_beg;    // per position: the row's first CSR index
+    std::vector<int> row_len;    // per position: the row's entries
+    std::vector<int> step_ptr;   // m + 1
+    std::vector<int> step_ent;   // per step: index of (i, k) inside row i
+    std::vector<int> step_diag;  // per step: CSR index of diag(k)
+    std::vector<int> pair_ptr;   // steps + 1
+    std::vector<int> pair_tgt;   // per pair: index of the target inside row i
+    std::vector<int> pair_src;   // per pair: CSR index of the source in row k
+    std::vector<int> long_pos;   // positions of the long rows, ascending
+    std::vector<int> long_ptr;   // nlevels + 1
+    std::vector<TrsmLaunch> launches;
+    int64_t steps = 0, pairs = 0, chain_rows = 0, max_pairs = 0;
+    int max_steps = 0, long_rows = 0, chain_launches = 0, chain_max_levels = 0;
+    // smfv_ilu0_analyse's out[] but [12] device bytes and [13] analysis ms
+    void stats(double out[ILU0_NSTATS]) const;
+};
+
+// The plan above, verified by replay before it is returned: every row in
+// exactly one launch, every step's row k in an earlier launch or an earlier
+// level of the same chain launch, the steps of a row strictly ascending in
+// column, every pair with equal columns on both sides and its source in row k
+// right of k, the pair count equal to an independent recount.  false (with
+// *err): a bad pattern or bad flags, a row with no diagonal entry (the first
+// is named), a column repeated inside a row (row and column are named), 2^31
+// pairs or more, or a failed replay.
+bool build_ilu0_plan(int m, const int *row_ptr, const int *col_idx, int flags, Ilu0Plan &out, std::string *err);
+
 }  // namespace smfv

@@ -103,6 +103,29 @@ class DeviceCSR:
             p.bind_values(stream)
         return p
 
+    def ilu0_plan(self, chain: str = "auto", thin_rows: int = 0) -> "Ilu0Plan":
+        """The cached ILU(0) plan of (chain, thin_rows), created on first use.
+        It holds no values: every factor() reads `values` as they are then."""
+        key = ("ilu0", chain, int(thin_rows))
+        p = self._plans.get(key)
+        if p is None:
+            p = self._plans[key] = Ilu0Plan(self, chain, thin_rows)
+        return p
+
+    def like(self, values: torch.Tensor) -> "DeviceCSR":
+        """A DeviceCSR of this pattern with other values: it shares the
+        pattern tensors and the host pattern with `self`, and has no plans."""
+        if not values.is_cuda or values.dtype != torch.float64 or tuple(values.shape) != (self.nnz,) \
+                or not values.is_contiguous():
+            raise ValueError(f"values must be a contiguous float64 HIP tensor of {self.nnz} entries")
+        B = object.__new__(DeviceCSR)
+        B.m, B.n, B.nnz = self.m, self.n, self.nnz
+        B.h_row_ptr, B.h_col_idx = self.h_row_ptr, self.h_col_idx
+        B.row_ptr, B.col_idx, B.values = self.row_ptr, self.col_idx, values
+        B.device = self.device
+        B._plans = {}
+        return B
+
     def values_version(self) -> tuple[int, int]:
         """(address, torch version counter) of `values`: changes with every
         in-place write torch performs and with a new tensor."""
@@ -399,6 +422,120 @@ def sptrsm(A: DeviceCSR, X: torch.Tensor, uplo: str = "lower", unit_diag: bool =
     """Y = T^-1 X on the device, T the lower / upper triangle of A, through
     A's cached solve plan for (K, uplo, unit_diag)."""
     return A.trsm_plan(X.shape[1], uplo, unit_diag, stream=stream).solve(X, Y, stream)
+
+
+ILU0_NO_CHAIN, ILU0_CHAIN_ALL = 4, 8  # SMFV_ILU0_*
+ILU0_STATS = 15  # SMFV_ILU0_STATS
+ILU0_STAT_NAMES = ("levels", "widest_level", "launches", "chain_launches", "chain_rows", "chain_max_levels", "steps",
+                   "pairs", "max_steps_per_row", "max_pairs_per_row", "long_rows", "lds_slot_entries", "plan_bytes",
+                   "analysis_ms", "thin_rows")
+
+
+def ilu0_flags(chain: str = "auto", thin_rows: int = 0) -> int:
+    """The SMFV_ILU0_* flags of a factorisation (ValueError for an unknown setting)."""
+    if chain not in ("auto", "off", "all"):
+        raise ValueError(f"chain must be 'auto', 'off' or 'all', got {chain!r}")
+    if not 0 <= int(thin_rows) <= 0xffff:
+        raise ValueError("thin_rows must be in [0, 65535]")
+    return {"auto": 0, "off": ILU0_NO_CHAIN, "all": ILU0_CHAIN_ALL}[chain] | (int(thin_rows) << 8)
+
+
+def _ilu0_stats(out) -> dict:
+    return {k: (float(out[i]) if k == "analysis_ms" else int(out[i])) for i, k in enumerate(ILU0_STAT_NAMES)}
+
+
+def ilu0_analyse(A: SparseMatrix, chain: str = "auto", thin_rows: int = 0) -> dict:
+    """The figures of a factorisation's host analysis (smfv_ilu0_analyse; no device)."""
+    ip = ctypes.POINTER(ctypes.c_int)
+    rp = np.ascontiguousarray(A.rowPtr, dtype=np.int32)
+    ci = np.ascontiguousarray(A.colIndices, dtype=np.int32)
+    out = (ctypes.c_double * ILU0_STATS)()
+    call("smfv_ilu0_analyse", A.numRows, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), ilu0_flags(chain, thin_rows), out)
+    return _ilu0_stats(out)
+
+
+class Ilu0Plan:
+    """The ILU(0) of the square A analysed once for its pattern
+    (include/smfv.h, smfv_ilu0_plan_*): factor() gives the factors in A's CSR
+    order -- strict-lower entries L (unit diagonal), the rest U --,
+    bit-identical to the sequential loop of the header.  chain / thin_rows:
+    as for TrsmPlan (A/B, tests).  The plan holds no values: factor() reads
+    A.values as they are when it runs."""
+
+    def __init__(self, A: DeviceCSR, chain: str = "auto", thin_rows: int = 0):
+        flags = ilu0_flags(chain, thin_rows)
+        if A.m != A.n:
+            raise ValueError(f"ILU(0) needs a square matrix, got {A.m} x {A.n}")
+        self.A, self.chain = A, chain
+        self._plan = ctypes.c_void_p()
+        ip = ctypes.POINTER(ctypes.c_int)
+        call("smfv_ilu0_plan_create", byref(self._plan), A.m, A.nnz, A.h_row_ptr.ctypes.data_as(ip),
+             A.h_col_idx.ctypes.data_as(ip), flags)
+
+    def bind_values(self, stream: torch.cuda.Stream | None = None) -> None:
+        """Nothing to do: the plan holds no values (DeviceCSR.values_changed()
+        calls this on every cached plan)."""
+
+    def stats(self) -> dict:
+        out = (ctypes.c_double * ILU0_STATS)()
+        call("smfv_ilu0_plan_stats", self._plan, out)
+        return _ilu0_stats(out)
+
+    def factor(self, out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """The factors of A.values (asynchronous on `stream`) into `out`,
+        which may be A.values itself (in place)."""
+        A = self.A
+        if out is None:
+            out = torch.empty_like(A.values)
+        if not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (A.nnz,) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 HIP tensor of {A.nnz} entries")
+        call("smfv_ilu0_plan_factor", self._plan, A.values.data_ptr(), out.data_ptr(), stream_handle(stream))
+        return out
+
+    def __del__(self):
+        try:
+            if self._plan:
+                call("smfv_ilu0_plan_destroy", self._plan)
+                self._plan = ctypes.c_void_p()
+        except Exception:
+            pass
+
+
+def ilu0(A: DeviceCSR, stream: torch.cuda.Stream | None = None) -> DeviceCSR:
+    """The ILU(0) factors of A as a matrix of A's pattern, through A's cached plan."""
+    return A.like(A.ilu0_plan().factor(stream=stream))
+
+
+class Ilu0Preconditioner:
+    """M^-1 = U^-1 L^-1 for m x K blocks: owns F = A.like(...), A's Ilu0Plan
+    and F's two solve plans (lower with a unit diagonal, upper).  refactor()
+    after A.values changed; apply() runs the two solves.  chain goes to all
+    three plans, thin_rows to the factorisation alone (the two kernels'
+    thresholds are measured apart)."""
+
+    def __init__(self, A: DeviceCSR, K: int, chain: str = "auto", stream: torch.cuda.Stream | None = None,
+                 thin_rows: int = 0):
+        self.A, self.K = A, int(K)
+        self.plan = Ilu0Plan(A, chain, thin_rows)
+        self.F = A.like(torch.empty_like(A.values))
+        self.plan.factor(self.F.values, stream)
+        self.lower = TrsmPlan(self.F, self.K, "lower", True, chain, stream=stream)
+        self.upper = TrsmPlan(self.F, self.K, "upper", False, chain, stream=stream)
+
+    def refactor(self, stream: torch.cuda.Stream | None = None) -> None:
+        """Factor A.values again and bind both solves to the new factors.  The
+        library writes F.values behind torch's back (no version counter
+        moves), so the solves are bound again explicitly."""
+        self.plan.factor(self.F.values, stream)
+        self.lower.bind_values(stream)
+        self.upper.bind_values(stream)
+
+    def apply(self, X: torch.Tensor, Y: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """Y = U^-1 L^-1 X (asynchronous on `stream`); the intermediate
+        L^-1 X lives in Y, which may be X itself."""
+        Y = self.lower.solve(X, Y, stream)
+        return self.upper.solve(Y, Y, stream)
 
 
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,
