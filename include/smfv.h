@@ -626,6 +626,95 @@ SMFV_API int smfv_ilu0_plan_destroy(smfv_ilu0_plan_t plan);
 SMFV_API int smfv_ilu0_analyse(int m, const int *h_row_ptr, const int *h_col_idx, int flags,
                                double out[SMFV_ILU0_STATS]);
 
+/* ---- Multicolour reordering: fewer levels for the solves and ILU(0) --------
+ * The solves and the factorisation above cost a fixed time per LEVEL of the
+ * triangle's dependency graph, whatever the schedule does; only another
+ * numbering of the matrix removes levels.  This family gives an ordering, the
+ * renumbered CSR and the device kernels that carry values and fat vectors
+ * into the new numbering and back.  No existing plan changes: the renumbered
+ * matrix B is an ordinary CSR for every plan family of this header.
+ *
+ * A multicolour ILU(0) is a DIFFERENT, usually somewhat weaker, preconditioner
+ * than the natural-order one (the standard trade on GPUs): the factors of B
+ * are not a renumbering of the factors of A.
+ *
+ * The ordering (smfv_order_multicolor; host only, no device needed; the values
+ * are not looked at).  The rule is fixed, so a caller can reproduce it:
+ *   - the graph is the pattern of A + A^T without the diagonal (A^T by
+ *     smfv_csr_transpose); repeated columns, unsorted rows and empty rows are
+ *     legal;
+ *   - rows are coloured in the order i = 0 .. m-1;
+ *   - color[i] is the smallest c >= 0 that no already-coloured neighbour
+ *     holds (only neighbours j < i can hold a colour): first-fit greedy;
+ *   - *ncolors = max + 1, and 0 for m = 0;
+ *   - perm lists the rows sorted by (color, i), a stable sort: new row i' is
+ *     old row perm[i'].
+ *   Consequence: in the renumbered matrix two rows of one colour never couple,
+ *   so its lower and its upper triangle each have at most *ncolors levels
+ *   (smfv_trsm_analyse, smfv_ilu0_analyse report them).
+ *   h_color may be NULL.  Refused with SMFV_ERR_INVALID and a message: a
+ *   column outside [0, m), a row_ptr that does not start at 0 or decreases,
+ *   unknown flag bits (none are defined: flags must be 0), NULL outputs.
+ *
+ * The renumbering (smfv_csr_permute_sym; host only).  B = P A P^T: row i' of
+ * B is row h_perm[i'] of A and a column c becomes inv[c] (inv the inverse of
+ * h_perm).  THE ENTRIES OF A ROW KEEP THE CALLER'S CSR ORDER; they are not
+ * sorted.  Entry j' of B is entry b_vperm[j'] of A (int, nnz < 2^31, like the
+ * entry map of smfv_csr_transpose).  Because the order is kept, every row of
+ * B is summed in the order of the row of A it came from:
+ *     B (P X) == P (A X)   bit for bit, on every bit-exact plan family.
+ *   Unsorted rows are legal input to the plans, the solves and ILU(0).
+ *   Refused: an h_perm that is not a permutation of [0, m) (the message names
+ *   the first offending position), a malformed pattern as above, NULL
+ *   outputs.
+ *
+ * The device plan (smfv_reorder_plan_*).  create validates both permutations
+ * on the host before any device call (h_perm a permutation of [0, m), h_vperm
+ * one of [0, nnz); h_vperm may be NULL with nnz = 0: a plan for rows only),
+ * uploads h_perm, its inverse and h_vperm, and synchronises.
+ *   values:  d_dst[j'] = d_src[vperm[j']], j' in [0, nnz)   (k_permute_vals)
+ *   rows, SMFV_REORDER_TO_NEW:  Y[i', 0:K] = X[perm[i'], 0:K]
+ *   rows, SMFV_REORDER_TO_OLD:  Y[r,  0:K] = X[inv[r],  0:K]
+ * so TO_OLD undoes TO_NEW.  Both directions are a gather with coalesced
+ * writes, by one kernel (k_permute_rows: a team of lanes covers the K columns
+ * of a row, several rows per wavefront and four rows in flight per team;
+ * 16-byte accesses when X, Y, ldx, ldy and K allow them, 8-byte otherwise;
+ * 64-bit element offsets).  Bit patterns are moved, not numbers: NaN payloads
+ * and the sign of zero survive.  Only the K columns are read and written:
+ * padding beyond K (ldx, ldy >= K) is neither read nor written.
+ *   Refused with SMFV_ERR_INVALID, nothing launched: d_Y == d_X, K < 1, a
+ *   NULL pointer, ldx < K or ldy < K, an unknown direction.  Any other
+ *   overlap of X and Y is undefined.
+ *   SMFV_REORDER_STORE_NT, or'ed to the direction, writes Y with non-temporal
+ *   stores (A/B; plain stores are the default, profiles/reorder/README.md).
+ *
+ * Streams: create allocates device memory and synchronises.  values and rows
+ * are asynchronous and graph-capturable -- no allocation, no synchronisation,
+ * no host read-back; the plan holds no values and has no bind.  A plan is not
+ * thread-safe.
+ *
+ * Out of scope: other orderings (largest-degree-first, RCM, nested
+ * dissection), balancing the sizes of the colours, permutations fused into
+ * the solve kernels, IC(0), distributed plans, the C++ drop-in, the CLI,
+ * bench.py. */
+typedef struct smfv_reorder_plan_s *smfv_reorder_plan_t;
+#define SMFV_REORDER_TO_NEW 1   /* Y[i'] = X[perm[i']] */
+#define SMFV_REORDER_TO_OLD 2   /* Y[r] = X[inv[r]] */
+#define SMFV_REORDER_STORE_NT 4 /* non-temporal stores of Y (A/B) */
+/* out[0] m, [1] nnz, [2] plan device bytes, [3] host validation + upload ms */
+#define SMFV_REORDER_STATS 4
+SMFV_API int smfv_order_multicolor(int m, const int *h_row_ptr, const int *h_col_idx, int flags, int *h_perm,
+                                   int *h_color, int *ncolors);
+SMFV_API int smfv_csr_permute_sym(int m, const int *h_row_ptr, const int *h_col_idx, const int *h_perm,
+                                  int *b_row_ptr, int *b_col_idx, int *b_vperm);
+SMFV_API int smfv_reorder_plan_create(smfv_reorder_plan_t *plan, int m, int64_t nnz, const int *h_perm,
+                                      const int *h_vperm);
+SMFV_API int smfv_reorder_plan_values(smfv_reorder_plan_t plan, const double *d_src, double *d_dst, void *stream);
+SMFV_API int smfv_reorder_plan_rows(smfv_reorder_plan_t plan, int direction, const double *d_X, int64_t ldx, int K,
+                                    double *d_Y, int64_t ldy, void *stream);
+SMFV_API int smfv_reorder_plan_stats(smfv_reorder_plan_t plan, double out[SMFV_REORDER_STATS]);
+SMFV_API int smfv_reorder_plan_destroy(smfv_reorder_plan_t plan);
+
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,
  * `bytes` (multiple of 16, 16-B aligned pointers) by a 16-byte-per-lane
  * non-temporal copy kernel.  Read + write bytes / time = the measured

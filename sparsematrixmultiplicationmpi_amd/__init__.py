@@ -5,6 +5,7 @@ AlexisBalayre/SparseMatrixMultiplicationMPI).
     Y[n x K] = A_csr^T * X[m x K]        (transposed plans, spmm_t)
     T Y = X, T a triangle of A_csr       (level-scheduled solves, sptrsm)
     L U ~ A_csr on A's pattern           (ILU(0), ilu0 / Ilu0Preconditioner)
+    B = P A P^T, few levels              (multicolour reordering, DeviceCSR.reordered)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -17,11 +18,13 @@ from .inputs import (  # noqa: F401
     SparseMatrix,
     areMatricesEqual,
     cop20k_surrogate,
+    csr_permute,
     csr_transpose,
     deserialize,
     gen_fem27,
     gen_random_rows,
     generateLargeFatVector,
+    multicolor_order,
     readMatrixMarketFile,
     serialize,
     writeMatrixMarketFile,
@@ -30,6 +33,7 @@ from .engine import (  # noqa: F401
     DeviceCSR,
     Ilu0Plan,
     Ilu0Preconditioner,
+    ReorderedCSR,
     SpmmPlan,
     TrsmPlan,
     VendorSpmm,

@@ -82,6 +82,13 @@ _SIGS = {
     "smfv_ilu0_plan_stats": (c_int, [c_void_p, _PD]),
     "smfv_ilu0_plan_destroy": (c_int, [c_void_p]),
     "smfv_ilu0_analyse": (c_int, [c_int, _PI, _PI, c_int, _PD]),
+    "smfv_order_multicolor": (c_int, [c_int, _PI, _PI, c_int, _PI, _PI, _PI]),
+    "smfv_csr_permute_sym": (c_int, [c_int, _PI, _PI, _PI, _PI, _PI, _PI]),
+    "smfv_reorder_plan_create": (c_int, [POINTER(c_void_p), c_int, c_int64, _PI, _PI]),
+    "smfv_reorder_plan_values": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "smfv_reorder_plan_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "smfv_reorder_plan_stats": (c_int, [c_void_p, _PD]),
+    "smfv_reorder_plan_destroy": (c_int, [c_void_p]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_spmm_colpanel_f64": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

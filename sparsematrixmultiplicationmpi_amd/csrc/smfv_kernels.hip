@@ -28,6 +28,8 @@
 //            block, the pivots of a bind; no counterpart in the reference
 //   k_ilu0_level, k_ilu0_chain   ILU(0) of A's values (smfv_ilu0_plan_*), on
 //            the lower solve's schedule; no counterpart in the reference
+//   k_permute_rows       fat vectors into another numbering of the rows and
+//            back (smfv_reorder_plan_*); no counterpart in the reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -4411,6 +4413,214 @@ SMFV_API int smfv_ilu0_plan_stats(smfv_ilu0_plan_t plan, double out[SMFV_ILU0_ST
 }
 
 SMFV_API int smfv_ilu0_plan_destroy(smfv_ilu0_plan_t plan)
+{
+    delete plan;
+    return SMFV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Reordering (smfv_reorder_plan_*, include/smfv.h): fat vectors into another
+// numbering of the rows and back, Y[i, 0:K] = X[idx[i], 0:K].  Both directions
+// are this one gather (idx = perm or its inverse), so a wavefront's stores
+// cover consecutive rows of Y.  A team of TEAM lanes covers the K columns of a
+// row, VEC doubles per lane (VEC = 2: 16-byte accesses, chosen on the host
+// when X, Y, ldx, ldy and K allow it), 256 / TEAM rows per pass of a block,
+// and R = 4 passes in flight: the four indices are read first, then per column
+// step the four rows are loaded before any is stored.  Bit patterns are
+// moved as 64-bit integers -- no floating-point instruction touches them, so
+// NaN payloads and the sign of zero survive.  idx and X are read once
+// (non-temporal loads, like every other read-once stream of this file); Y is
+// stored plain by default (the next solve reads it) or, for the A/B of
+// profiles/reorder/README.md, non-temporal (NT).  Element offsets are 64-bit.
+// No LDS, no scratch, no atomics.
+// ---------------------------------------------------------------------------
+namespace smfv {
+
+typedef unsigned long long perm_u1;
+typedef unsigned long long perm_u2 __attribute__((ext_vector_type(2)));
+template <int VEC> struct PermT;
+template <> struct PermT<1> {
+    using T = perm_u1;
+};
+template <> struct PermT<2> {
+    using T = perm_u2;
+};
+
+// FULL: every one of the block's R * RPB rows exists (block-uniform), so the
+// loads and the stores carry no per-row condition and issue back to back.
+template <int TEAM, int VEC, bool NT, bool FULL>
+__device__ __forceinline__ void permute_rows_body(int m, const int *__restrict__ idx, const double *__restrict__ X,
+                                                  int64_t ldx, int K, double *__restrict__ Y, int64_t ldy, int64_t r0)
+{
+    using T = typename PermT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, R = 4;
+    const int tl = (int)threadIdx.x & (TEAM - 1);
+    const T *src[R];
+    T *dst[R];
+    bool ok[R];
+    int s[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const int64_t row = r0 + u * RPB;
+        ok[u] = FULL || row < m;
+        // a row past the end reads the last row's index (a valid address) and stores nothing
+        s[u] = __builtin_nontemporal_load(idx + (FULL ? row : min(row, (int64_t)m - 1)));
+        dst[u] = reinterpret_cast<T *>(Y + row * ldy);
+    }
+#pragma unroll
+    for (int u = 0; u < R; ++u) src[u] = reinterpret_cast<const T *>(X + (int64_t)s[u] * ldx);
+    const int nv = K / VEC;  // VEC == 2 only for an even K
+    for (int c = tl; c < nv; c += TEAM) {
+        T v[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) v[u] = __builtin_nontemporal_load(src[u] + c);
+#pragma unroll
+        for (int u = 0; u < R; ++u)
+            if (ok[u]) {
+                if constexpr (NT) __builtin_nontemporal_store(v[u], dst[u] + c);
+                else dst[u][c] = v[u];
+            }
+    }
+}
+
+template <int TEAM, int VEC, bool NT>
+__global__ __launch_bounds__(256) void k_permute_rows(int m, const int *__restrict__ idx, const double *__restrict__ X,
+                                                      int64_t ldx, int K, double *__restrict__ Y, int64_t ldy)
+{
+    constexpr int RPB = 256 / TEAM, R = 4;
+    const int64_t b0 = (int64_t)blockIdx.x * (RPB * R), r0 = b0 + (int)threadIdx.x / TEAM;
+    if (b0 + RPB * R <= m) permute_rows_body<TEAM, VEC, NT, true>(m, idx, X, ldx, K, Y, ldy, r0);
+    else permute_rows_body<TEAM, VEC, NT, false>(m, idx, X, ldx, K, Y, ldy, r0);
+}
+
+}  // namespace smfv
+
+struct smfv_reorder_plan_s {
+    int m = 0;
+    int64_t nnz = 0;
+    int *perm = nullptr, *inv = nullptr, *vperm = nullptr;
+    size_t dev_bytes = 0;
+    double create_ms = 0.0;
+    ~smfv_reorder_plan_s()
+    {
+        for (void *q : {(void *)perm, (void *)inv, (void *)vperm})
+            if (q) (void)hipFree(q);
+    }
+};
+
+namespace {
+
+template <bool NT>
+int permute_rows_launch(int m, const int *idx, const double *X, int64_t ldx, int K, double *Y, int64_t ldy, hipStream_t st)
+{
+    const int vec = pick_vec(X, ldx, Y, ldy, K);
+    const int team = pick_team(K, vec);
+    const int rows_per_block = 256 / team * 4;
+    const unsigned nblk = (unsigned)(((int64_t)m + rows_per_block - 1) / rows_per_block);
+#define LP(T_, V_) hipLaunchKernelGGL((k_permute_rows<T_, V_, NT>), dim3(nblk), dim3(256), 0, st, m, idx, X, ldx, K, Y, ldy)
+    SMFV_TEAM_SWITCH(team, vec, LP)
+#undef LP
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+SMFV_API int smfv_order_multicolor(int m, const int *h_row_ptr, const int *h_col_idx, int flags, int *h_perm,
+                                   int *h_color, int *ncolors)
+{
+    std::string err;
+    if (!order_multicolor(m, h_row_ptr, h_col_idx, flags, h_perm, h_color, ncolors, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_csr_permute_sym(int m, const int *h_row_ptr, const int *h_col_idx, const int *h_perm, int *b_row_ptr,
+                                  int *b_col_idx, int *b_vperm)
+{
+    std::string err;
+    if (!csr_permute_sym(m, h_row_ptr, h_col_idx, h_perm, b_row_ptr, b_col_idx, b_vperm, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_reorder_plan_create(smfv_reorder_plan_t *out, int m, int64_t nnz, const int *h_perm, const int *h_vperm)
+{
+    SMFV_REQUIRE(out, "null plan pointer");
+    SMFV_REQUIRE(m >= 0 && nnz >= 0 && nnz <= 0x7fffffff, "reorder: bad sizes");
+    SMFV_REQUIRE(h_vperm || nnz == 0, "reorder: null vperm with nnz = %lld (a plan for rows only takes nnz = 0)", (long long)nnz);
+    const auto t_start = std::chrono::steady_clock::now();
+    // both permutations are checked on the host before the first device call
+    std::vector<int> inv((size_t)m);
+    std::string err;
+    if (!check_permutation(m, h_perm, inv.data(), "reorder: perm", &err) ||
+        !check_permutation(nnz, h_vperm, nullptr, "reorder: vperm", &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    auto *p = new smfv_reorder_plan_s;
+    p->m = m;
+    p->nnz = nnz;
+    int rc = upload(&p->perm, std::vector<int>(h_perm, h_perm + m), p->dev_bytes);
+    if (!rc) rc = upload(&p->inv, inv, p->dev_bytes);
+    if (!rc) rc = upload(&p->vperm, std::vector<int>(h_vperm, h_vperm + nnz), p->dev_bytes);
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    p->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    *out = p;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_reorder_plan_values(smfv_reorder_plan_t plan, const double *d_src, double *d_dst, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    if (plan->nnz == 0) return SMFV_OK;
+    SMFV_REQUIRE(d_src && d_dst, "reorder: null values");
+    SMFV_REQUIRE(d_src != d_dst, "reorder: values cannot be permuted in place");
+    hipLaunchKernelGGL(k_permute_vals, dim3((unsigned)((plan->nnz + 511) / 512)), dim3(256), 0, as_stream(stream), plan->nnz,
+                       plan->vperm, d_src, d_dst);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_reorder_plan_rows(smfv_reorder_plan_t plan, int direction, const double *d_X, int64_t ldx, int K,
+                                    double *d_Y, int64_t ldy, void *stream)
+{
+    SMFV_REQUIRE(plan, "null plan");
+    const int dir = direction & ~SMFV_REORDER_STORE_NT;
+    SMFV_REQUIRE(dir == SMFV_REORDER_TO_NEW || dir == SMFV_REORDER_TO_OLD, "reorder: unknown direction %d", direction);
+    SMFV_REQUIRE(K >= 1, "reorder: K = %d, must be at least 1", K);
+    SMFV_REQUIRE(ldx >= K && ldy >= K, "reorder: leading dimension smaller than K");
+    SMFV_REQUIRE(d_X && d_Y, "reorder: null X / Y");
+    SMFV_REQUIRE(d_X != d_Y, "reorder: Y must not be X (the rows cannot be permuted in place)");
+    if (plan->m == 0) return SMFV_OK;
+    const int *idx = dir == SMFV_REORDER_TO_NEW ? plan->perm : plan->inv;
+    hipStream_t st = as_stream(stream);
+    return (direction & SMFV_REORDER_STORE_NT) ? permute_rows_launch<true>(plan->m, idx, d_X, ldx, K, d_Y, ldy, st)
+                                               : permute_rows_launch<false>(plan->m, idx, d_X, ldx, K, d_Y, ldy, st);
+}
+
+SMFV_API int smfv_reorder_plan_stats(smfv_reorder_plan_t plan, double out[SMFV_REORDER_STATS])
+{
+    SMFV_REQUIRE(plan && out, "null argument");
+    out[0] = plan->m;
+    out[1] = (double)plan->nnz;
+    out[2] = (double)plan->dev_bytes;
+    out[3] = plan->create_ms;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_reorder_plan_destroy(smfv_reorder_plan_t plan)
 {
     delete plan;
     return SMFV_OK;

@@ -2138,4 +2138,120 @@ bool build_ilu0_plan(int m, const int *rp, const int *ci, int flags, Ilu0Plan &P
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Multicolour ordering and symmetric renumbering (smfv_plan.h).
+// ---------------------------------------------------------------------------
+namespace {
+
+// the solves' pattern check, under this family's name
+bool reorder_validate(const char *name, int m, const int *rp, const int *ci, std::string *err)
+{
+    std::string e;
+    if (trsm_validate(m, rp, ci, &e)) return true;
+    if (err) *err = name + e.substr(4);
+    return false;
+}
+
+}  // namespace
+
+bool order_multicolor(int m, const int *rp, const int *ci, int flags, int *perm, int *color, int *ncolors, std::string *err)
+{
+    if (flags & ~ORDER_FLAGS) return trsm_fail(err, "order: unknown flags %lld (known: %lld)", flags, ORDER_FLAGS);
+    if (!ncolors || (m > 0 && !perm)) return trsm_fail(err, "order: null perm / ncolors (m = %lld, %lld)", m, 0);
+    if (!reorder_validate("order", m, rp, ci, err)) return false;
+    const int64_t nnz = rp[m];
+    // A^T's pattern: row i of it lists the rows of A that name column i
+    std::vector<int> t_rp((size_t)m + 1), t_ci((size_t)nnz), t_perm((size_t)nnz);
+    {
+        std::string e;
+        if (!csr_transpose(m, m, rp, ci, t_rp.data(), t_ci.data(), t_perm.data(), &e)) {
+            if (err) *err = "order: " + e;
+            return false;
+        }
+    }
+    std::vector<int>().swap(t_perm);
+    std::vector<int> own;
+    if (!color) {
+        own.resize((size_t)m);
+        color = own.data();
+    }
+    // row i sees the colours of its neighbours j < i; taken[c] == i marks c.
+    // A row has at most i coloured neighbours, so its colour is at most i.
+    std::vector<int> taken((size_t)m + 1, -1);
+    int nc = 0;
+    for (int i = 0; i < m; ++i) {
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j)
+            if (ci[j] < i) taken[(size_t)color[ci[j]]] = i;
+        for (int64_t j = t_rp[i]; j < t_rp[i + 1]; ++j)
+            if (t_ci[j] < i) taken[(size_t)color[t_ci[j]]] = i;
+        int c = 0;
+        while (taken[(size_t)c] == i) ++c;
+        color[i] = c;
+        nc = std::max(nc, c + 1);
+    }
+    // rows by (colour, row): a stable counting sort
+    std::vector<int> next((size_t)nc + 1, 0);
+    for (int i = 0; i < m; ++i) ++next[(size_t)color[i] + 1];
+    for (int c = 0; c < nc; ++c) next[(size_t)c + 1] += next[(size_t)c];
+    for (int i = 0; i < m; ++i) perm[next[(size_t)color[i]]++] = i;
+    // replay: perm a permutation in (colour, row) order; no entry of A off the
+    // diagonal joins two rows of one colour (A^T's entries are A's)
+    if (!check_permutation(m, perm, nullptr, "order: replay: perm", err)) return false;
+    for (int p = 1; p < m; ++p) {
+        const int a = perm[p - 1], b = perm[p];
+        if (color[a] > color[b] || (color[a] == color[b] && a >= b))
+            return trsm_fail(err, "order: replay: position %lld out of (colour, row) order (row %lld)", p, b);
+    }
+    for (int i = 0; i < m; ++i)
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j)
+            if (ci[j] != i && color[ci[j]] == color[i])
+                return trsm_fail(err, "order: replay: rows %lld and %lld share a colour", i, ci[j]);
+    *ncolors = nc;
+    return true;
+}
+
+bool check_permutation(int64_t m, const int *perm, int *inv, const char *what, std::string *err)
+{
+    auto fail = [&](const char *fmt, long long a, long long b) {
+        if (err) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, fmt, what, a, b);
+            *err = buf;
+        }
+        return false;
+    };
+    if (m < 0) return fail("%s: bad size %lld (%lld)", m, 0);
+    if (m > 0 && !perm) return fail("%s: null array (%lld entries, %lld)", m, 0);
+    std::vector<uint8_t> seen((size_t)m, 0);
+    for (int64_t p = 0; p < m; ++p) {
+        const int64_t r = perm[p];
+        if (r < 0 || r >= m) return fail("%s: position %lld holds %lld, outside the range", p, r);
+        if (seen[(size_t)r]) return fail("%s: position %lld holds %lld a second time", p, r);
+        seen[(size_t)r] = 1;
+        if (inv) inv[r] = (int)p;
+    }
+    return true;
+}
+
+bool csr_permute_sym(int m, const int *rp, const int *ci, const int *perm, int *b_rp, int *b_ci, int *b_vperm, std::string *err)
+{
+    if (!reorder_validate("permute", m, rp, ci, err)) return false;
+    const int64_t nnz = rp[m];
+    if (!b_rp || (nnz > 0 && (!b_ci || !b_vperm))) return trsm_fail(err, "permute: null output (m = %lld, nnz = %lld)", m, nnz);
+    std::vector<int> inv((size_t)m);
+    if (!check_permutation(m, perm, inv.data(), "permute: perm", err)) return false;
+    int64_t d = 0;
+    b_rp[0] = 0;
+    for (int i = 0; i < m; ++i) {
+        const int r = perm[i];
+        for (int64_t j = rp[r]; j < rp[r + 1]; ++j, ++d) {
+            b_ci[d] = inv[(size_t)ci[j]];
+            b_vperm[d] = (int)j;
+        }
+        b_rp[i + 1] = (int)d;
+    }
+    if (d != nnz) return trsm_fail(err, "permute: %lld entries written, the pattern holds %lld", (long long)d, (long long)nnz);
+    return true;
+}
+
 }  // namespace smfv

@@ -459,4 +459,37 @@ struct Ilu0Plan {
 // pairs or more, or a failed replay.
 bool build_ilu0_plan(int m, const int *row_ptr, const int *col_idx, int flags, Ilu0Plan &out, std::string *err);
 
+// ---------------------------------------------------------------------------
+// Multicolour ordering and symmetric renumbering of a square CSR pattern
+// (smfv_order_multicolor, smfv_csr_permute_sym, smfv_reorder_plan_*,
+// include/smfv.h): fewer levels for the solves and ILU(0) above.  Host only;
+// the values are not looked at.
+// ---------------------------------------------------------------------------
+constexpr int ORDER_FLAGS = 0;  // no flag bits are defined
+
+// First-fit greedy colouring in natural order of the graph of A + A^T without
+// the diagonal (A^T from csr_transpose): color[i] is the smallest c >= 0 that
+// no neighbour j < i holds; *ncolors = max + 1 (0 for m = 0); perm lists the
+// rows sorted by (color, row), a stable counting sort: new row i' is old row
+// perm[i'].  color may be NULL.  Repeated columns, unsorted and empty rows are
+// legal.  Verified by replay before it is returned: perm a permutation in
+// (color, row) order, no entry of A off the diagonal joining two rows of one
+// colour.  false (with *err): a bad pattern, unknown flags, NULL outputs, or a
+// failed replay.
+bool order_multicolor(int m, const int *row_ptr, const int *col_idx, int flags, int *perm, int *color, int *ncolors,
+                      std::string *err);
+
+// perm a permutation of [0, m)?  inv (m entries, may be NULL) receives its
+// inverse.  false (with *err naming the first offending position) otherwise.
+bool check_permutation(int64_t m, const int *perm, int *inv, const char *what, std::string *err);
+
+// B = P A P^T: row i' of B is row perm[i'] of A, a column c becomes inv[c],
+// and the entries of a row KEEP the caller's CSR order (they are not sorted):
+// entry j' of B is entry b_vperm[j'] of A, ascending inside every row of B.
+// b_row_ptr[m + 1], b_col_idx[nnz], b_vperm[nnz].  false (with *err): a bad
+// pattern, a perm that is no permutation (the first offending position is
+// named), NULL outputs.
+bool csr_permute_sym(int m, const int *row_ptr, const int *col_idx, const int *perm, int *b_row_ptr, int *b_col_idx,
+                     int *b_vperm, std::string *err);
+
 }  // namespace smfv

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import call
-from .inputs import SparseMatrix
+from .inputs import SparseMatrix, csr_permute_pattern, multicolor_order_pattern
 
 
 class Variant(IntEnum):
@@ -125,6 +125,14 @@ class DeviceCSR:
         B.device = self.device
         B._plans = {}
         return B
+
+    def reordered(self, order="multicolor") -> "ReorderedCSR":
+        """This square matrix under another numbering of its rows and columns
+        (ReorderedCSR): order="multicolor" (the library's greedy colouring,
+        which cuts the levels of the solves and of ILU(0) to the number of
+        colours) or an explicit permutation array (new row i is old row
+        order[i])."""
+        return ReorderedCSR(self, order)
 
     def values_version(self) -> tuple[int, int]:
         """(address, torch version counter) of `values`: changes with every
@@ -506,18 +514,129 @@ def ilu0(A: DeviceCSR, stream: torch.cuda.Stream | None = None) -> DeviceCSR:
     return A.like(A.ilu0_plan().factor(stream=stream))
 
 
+REORDER_TO_NEW, REORDER_TO_OLD, REORDER_STORE_NT = 1, 2, 4  # SMFV_REORDER_*
+REORDER_STATS = 4  # SMFV_REORDER_STATS
+REORDER_STAT_NAMES = ("m", "nnz", "plan_bytes", "create_ms")
+
+
+class ReorderedCSR:
+    """The square A under another numbering (include/smfv.h,
+    smfv_reorder_plan_*): B = P A P^T with row i of B = row perm[i] of A and
+    every row's entries in A's CSR order, so B (P X) == P (A X) bit for bit.
+    order: "multicolor" (smfv_order_multicolor; `ncolors` and `color` are set,
+    and B's triangles have at most `ncolors` levels) or a permutation array
+    (`ncolors` is None).  B is a DeviceCSR with plans of its own; its values
+    follow A.values: refresh() carries them over on the device, and `B`
+    refreshes by itself when A.values_version() has moved.  to_new / to_old
+    carry m x K blocks into B's numbering and back."""
+
+    def __init__(self, A: DeviceCSR, order="multicolor"):
+        if A.m != A.n:
+            raise ValueError(f"a reordering needs a square matrix, got {A.m} x {A.n}")
+        self.A = A
+        if isinstance(order, str):
+            if order != "multicolor":
+                raise ValueError(f"order must be 'multicolor' or a permutation array, got {order!r}")
+            self.perm, self.color, self.ncolors = multicolor_order_pattern(A.m, A.h_row_ptr, A.h_col_idx)
+        else:
+            self.perm, self.color, self.ncolors = np.ascontiguousarray(order, dtype=np.int32), None, None
+        b_rp, b_ci, self.vperm = csr_permute_pattern(A.m, A.h_row_ptr, A.h_col_idx, self.perm)
+        self._plan = ctypes.c_void_p()
+        ip = ctypes.POINTER(ctypes.c_int)
+        call("smfv_reorder_plan_create", byref(self._plan), A.m, A.nnz, self.perm.ctypes.data_as(ip),
+             self.vperm.ctypes.data_as(ip))
+        B = object.__new__(DeviceCSR)
+        B.m, B.n, B.nnz = A.m, A.n, A.nnz
+        B.h_row_ptr, B.h_col_idx = b_rp, b_ci
+        B.row_ptr = torch.from_numpy(b_rp).to(A.device)
+        B.col_idx = torch.from_numpy(b_ci).to(A.device)
+        B.values = torch.empty_like(A.values)
+        B.device = A.device
+        B._plans = {}
+        self._B = B
+        self.refresh()
+
+    @property
+    def B(self) -> DeviceCSR:
+        """The renumbered matrix, its values (and its cached plans) brought up
+        to A.values first if those changed since the last refresh."""
+        if self._version != self.A.values_version():
+            self.refresh()
+        return self._B
+
+    def refresh(self, stream: torch.cuda.Stream | None = None) -> None:
+        """B.values = A.values[vperm] on the device (asynchronous on `stream`),
+        then B.values_changed(): the library writes B.values behind torch's
+        version counter, so B's cached plans are bound again explicitly."""
+        call("smfv_reorder_plan_values", self._plan, self.A.values.data_ptr(), self._B.values.data_ptr(),
+             stream_handle(stream))
+        self._version = self.A.values_version()
+        self._B.values_changed(stream)
+
+    def _rows(self, direction: int, X: torch.Tensor, out: torch.Tensor | None, stream, nt: bool) -> torch.Tensor:
+        m = self.A.m
+        if X.dim() != 2 or X.shape[1] < 1:
+            raise ValueError(f"X must have shape ({m}, K) with K >= 1, got {tuple(X.shape)}")
+        K = X.shape[1]
+        if out is None:
+            out = torch.empty((m, K), dtype=torch.float64, device=self.A.device)
+        ldx = _check_dense(X, m, K, "X")
+        ldy = _check_dense(out, m, K, "out")
+        call("smfv_reorder_plan_rows", self._plan, direction | (REORDER_STORE_NT if nt else 0), X.data_ptr(), ldx, K,
+             out.data_ptr(), ldy, stream_handle(stream))
+        return out
+
+    def to_new(self, X: torch.Tensor, out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+               nt: bool = False) -> torch.Tensor:
+        """out[i] = X[perm[i]]: an m x K block into B's numbering (asynchronous
+        on `stream`; out must not be X).  nt: non-temporal stores (A/B)."""
+        return self._rows(REORDER_TO_NEW, X, out, stream, nt)
+
+    def to_old(self, Y: torch.Tensor, out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+               nt: bool = False) -> torch.Tensor:
+        """out[perm[i]] = Y[i]: back into A's numbering; undoes to_new."""
+        return self._rows(REORDER_TO_OLD, Y, out, stream, nt)
+
+    def stats(self) -> dict:
+        out = (ctypes.c_double * REORDER_STATS)()
+        call("smfv_reorder_plan_stats", self._plan, out)
+        return {k: (float(out[i]) if k == "create_ms" else int(out[i])) for i, k in enumerate(REORDER_STAT_NAMES)}
+
+    def __del__(self):
+        try:
+            if self._plan:
+                call("smfv_reorder_plan_destroy", self._plan)
+                self._plan = ctypes.c_void_p()
+        except Exception:
+            pass
+
+
 class Ilu0Preconditioner:
     """M^-1 = U^-1 L^-1 for m x K blocks: owns F = A.like(...), A's Ilu0Plan
     and F's two solve plans (lower with a unit diagonal, upper).  refactor()
     after A.values changed; apply() runs the two solves.  chain goes to all
     three plans, thin_rows to the factorisation alone (the two kernels'
-    thresholds are measured apart)."""
+    thresholds are measured apart).
+    reorder: None (natural order), "multicolor", a permutation array or a
+    ReorderedCSR of A: the preconditioner then factors B = P A P^T and solves
+    on B's factors, and apply() is to_new, the two solves, to_old, through a
+    buffer allocated once (`R` is the ReorderedCSR).  A multicolour ILU(0) has
+    as many levels as colours instead of the natural order's hundreds or
+    thousands, and is a different, usually somewhat weaker, preconditioner."""
 
     def __init__(self, A: DeviceCSR, K: int, chain: str = "auto", stream: torch.cuda.Stream | None = None,
-                 thin_rows: int = 0):
+                 thin_rows: int = 0, reorder=None):
         self.A, self.K = A, int(K)
-        self.plan = Ilu0Plan(A, chain, thin_rows)
-        self.F = A.like(torch.empty_like(A.values))
+        self.R = None
+        if reorder is not None:
+            self.R = reorder if isinstance(reorder, ReorderedCSR) else ReorderedCSR(A, reorder)
+            if self.R.A is not A:
+                raise ValueError("reorder is a ReorderedCSR of another matrix")
+            self.R.refresh(stream)
+            self._w = torch.empty((A.m, self.K), dtype=torch.float64, device=A.device)
+        M = self.M = A if self.R is None else self.R._B
+        self.plan = Ilu0Plan(M, chain, thin_rows)
+        self.F = M.like(torch.empty_like(M.values))
         self.plan.factor(self.F.values, stream)
         self.lower = TrsmPlan(self.F, self.K, "lower", True, chain, stream=stream)
         self.upper = TrsmPlan(self.F, self.K, "upper", False, chain, stream=stream)
@@ -525,7 +644,10 @@ class Ilu0Preconditioner:
     def refactor(self, stream: torch.cuda.Stream | None = None) -> None:
         """Factor A.values again and bind both solves to the new factors.  The
         library writes F.values behind torch's back (no version counter
-        moves), so the solves are bound again explicitly."""
+        moves), so the solves are bound again explicitly.  With a reordering,
+        B's values are refreshed from A's first."""
+        if self.R is not None:
+            self.R.refresh(stream)
         self.plan.factor(self.F.values, stream)
         self.lower.bind_values(stream)
         self.upper.bind_values(stream)
@@ -533,9 +655,16 @@ class Ilu0Preconditioner:
     def apply(self, X: torch.Tensor, Y: torch.Tensor | None = None,
               stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         """Y = U^-1 L^-1 X (asynchronous on `stream`); the intermediate
-        L^-1 X lives in Y, which may be X itself."""
-        Y = self.lower.solve(X, Y, stream)
-        return self.upper.solve(Y, Y, stream)
+        L^-1 X lives in Y, which may be X itself.  With a reordering:
+        Y = P^T U^-1 L^-1 P X with B's factors, the intermediates in the
+        preconditioner's own buffer."""
+        if self.R is None:
+            Y = self.lower.solve(X, Y, stream)
+            return self.upper.solve(Y, Y, stream)
+        W = self.R.to_new(X, self._w, stream)
+        self.lower.solve(W, W, stream)
+        self.upper.solve(W, W, stream)
+        return self.R.to_old(W, Y, stream)
 
 
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,

@@ -229,3 +229,54 @@ def csr_transpose(A: SparseMatrix) -> tuple[SparseMatrix, np.ndarray]:
     call("smfv_csr_transpose", A.numRows, A.numCols, _ip(rp), _ip(ci), _ip(t_rp), _ip(t_ci), _ip(perm))
     return SparseMatrix(values=np.asarray(A.values, dtype=np.float64)[perm], colIndices=t_ci, rowPtr=t_rp,
                         numRows=A.numCols, numCols=A.numRows), perm
+
+
+def _square_pattern(A: SparseMatrix) -> tuple[np.ndarray, np.ndarray]:
+    rp = np.ascontiguousarray(A.rowPtr, dtype=np.int32)
+    ci = np.ascontiguousarray(A.colIndices, dtype=np.int32)
+    if A.numRows != A.numCols:
+        raise ValueError(f"a reordering needs a square matrix, got {A.numRows} x {A.numCols}")
+    if len(rp) != A.numRows + 1 or len(ci) != (int(rp[-1]) if len(rp) else 0):
+        raise ValueError("malformed rowPtr / colIndices")
+    return rp, ci
+
+
+def multicolor_order_pattern(m: int, rp: np.ndarray, ci: np.ndarray) -> tuple[np.ndarray, np.ndarray, int]:
+    """(perm, color, ncolors) of smfv_order_multicolor for an int32 pattern."""
+    perm, color = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    ncolors = c_int(-1)
+    call("smfv_order_multicolor", m, _ip(rp), _ip(ci), 0, _ip(perm), _ip(color), byref(ncolors))
+    return perm, color, ncolors.value
+
+
+def csr_permute_pattern(m: int, rp: np.ndarray, ci: np.ndarray, perm) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(b_row_ptr, b_col_idx, vperm) of smfv_csr_permute_sym for an int32 pattern."""
+    perm = np.ascontiguousarray(perm, dtype=np.int32)
+    if perm.shape != (m,):
+        raise ValueError(f"perm must hold {m} entries, got shape {perm.shape}")
+    b_rp = np.zeros(m + 1, np.int32)
+    b_ci, vperm = np.zeros(len(ci), np.int32), np.zeros(len(ci), np.int32)
+    call("smfv_csr_permute_sym", m, _ip(rp), _ip(ci), _ip(perm), _ip(b_rp), _ip(b_ci), _ip(vperm))
+    return b_rp, b_ci, vperm
+
+
+def multicolor_order(A: SparseMatrix) -> tuple[np.ndarray, np.ndarray]:
+    """(perm, color) of the library's multicolour ordering
+    (smfv_order_multicolor, host only): a first-fit greedy colouring of the
+    graph of A + A^T in natural order; perm lists the rows by (color, row), new
+    row i is old row perm[i].  The number of colours is color.max() + 1."""
+    rp, ci = _square_pattern(A)
+    perm, color, _ = multicolor_order_pattern(A.numRows, rp, ci)
+    return perm, color
+
+
+def csr_permute(A: SparseMatrix, perm: np.ndarray) -> tuple[SparseMatrix, np.ndarray]:
+    """(B, vperm) with B = P A P^T by the library (smfv_csr_permute_sym, host
+    only): row i of B is row perm[i] of A, a column c becomes inv[c], and the
+    entries of a row keep A's CSR order (they are not sorted, unlike
+    permute_symmetric); entry j of B is entry vperm[j] of A."""
+    rp, ci = _square_pattern(A)
+    m = A.numRows
+    b_rp, b_ci, vperm = csr_permute_pattern(m, rp, ci, perm)
+    return SparseMatrix(values=np.asarray(A.values, dtype=np.float64)[vperm], colIndices=b_ci, rowPtr=b_rp,
+                        numRows=m, numCols=m), vperm
