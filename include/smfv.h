@@ -715,6 +715,86 @@ SMFV_API int smfv_reorder_plan_rows(smfv_reorder_plan_t plan, int direction, con
 SMFV_API int smfv_reorder_plan_stats(smfv_reorder_plan_t plan, double out[SMFV_REORDER_STATS]);
 SMFV_API int smfv_reorder_plan_destroy(smfv_reorder_plan_t plan);
 
+/* ---- Block vectors: column dots and per-column scaled updates --------------
+ * The pieces a preconditioned block Krylov iteration needs besides A X and
+ * M^-1 X, on m x K row-major blocks with leading dimensions >= K: one dot
+ * product per column in a FIXED SUMMATION ORDER, and updates Y += s X,
+ * Y = X + s Y whose per-column scalars s[j] stay on the device (a quotient of
+ * two earlier dots), so no host read sits between a dot and its use and a
+ * whole iteration captures into a graph.  libsmfv is built with
+ * -ffp-contract=off: every product and every sum below is rounded on its own,
+ * there is never an FMA.
+ *
+ * The column-dot rule (smfv_coldot_rule returns its two constants,
+ * CHUNK = 512 rows and STRANDS = 32; smfv_coldot_host is the rule in plain
+ * C++).  d[j] = coldot(X, Y)[j]:
+ *   - rows are cut into chunks of CHUNK consecutive rows; the last may be
+ *     short;
+ *   - inside chunk c, strand s (0 <= s < STRANDS) starts at +0.0 and, for
+ *     t = 0, 1, ... in ascending order, adds fl(X[r,j] * Y[r,j]) for
+ *     r = c*CHUNK + s + t*STRANDS while r is inside the chunk and below m;
+ *   - the strands combine by the shuffle-down tree: for h = 16, 8, 4, 2, 1
+ *     (STRANDS/2 downwards): v[s] = fl(v[s] + v[s+h]) for s < h; v[0] is the
+ *     chunk's partial;
+ *   - d[j] starts at +0.0 and adds the chunk partials in ascending chunk
+ *     order.  m = 0 gives +0.0.
+ *   An accumulator that starts at +0.0 never becomes -0.0, so a missing row
+ *   equals a product of +0.0 (a restatement may zero-pad to a multiple of
+ *   CHUNK), and no result is ever -0.0.  The result depends on (m, K, the
+ *   data) only -- not on the grid, the team width, the 8- / 16-byte access
+ *   path or the device.  NaN in gives NaN out (payloads are not promised),
+ *   inf - inf is NaN, overflow goes to +-inf.  X may be Y.
+ *   On the device: k_coldot_partial writes one partial per (chunk, column)
+ *   into the caller's workspace (smfv_coldot_workspace_bytes:
+ *   max(1, chunks) * K doubles; it needs no zeroing, no stale entry is ever
+ *   read), k_coldot_final adds them in chunk order.  Both are launched on
+ *   every call, also for m = 0.  No atomics, flags or cooperative launch: the
+ *   hand-over is the kernel boundary.  Only the K columns are read.
+ *
+ * The scalar rule.  s[j] = fl(num[j] / den[j]), a true IEEE division;
+ * d_den == NULL: s[j] = num[j].  SMFV_COL_NEGATE flips the sign of s[j]
+ * (exact).  SMFV_COL_ZERO_DEN: s[j] = +0.0 wherever den[j] == 0 (either
+ * zero), before the flip -- the breakdown guard of a column whose residual is
+ * exactly zero; without it plain IEEE applies (x/0 = +-inf, 0/0 = NaN).
+ * Every lane forms its own quotient from the device arrays.
+ *   axpy:  Y[i,j] = fl(Y[i,j] + fl(s[j] * X[i,j]))
+ *   xpay:  Y[i,j] = fl(X[i,j] + fl(s[j] * Y[i,j]))
+ *   X may be Y (in place); any other overlap is undefined.  m = 0 launches
+ *   nothing.
+ *   smfv_pcg_update_f64, the fused update of a PCG iteration, in one pass over
+ *   four blocks: X += s P, R += (-s) Q, then rr = coldot(R, R) on the new R.
+ *   It is bit-identical to smfv_col_axpy_f64(flags) on (P, X),
+ *   smfv_col_axpy_f64(flags ^ SMFV_COL_NEGATE) on (Q, R) and
+ *   smfv_coldot_f64(R, R), and launches k_pcg_update and k_coldot_final on
+ *   every call.
+ *
+ * Refused with SMFV_ERR_INVALID before any device call: K < 1, m < 0, a
+ * leading dimension below K, unknown flag bits, a NULL num / out / workspace,
+ * a NULL block with m > 0, and in the fused call any two of P, Q, X, R that
+ * share an element (exact aliasing included).
+ *
+ * Streams: every call is asynchronous on `stream` and graph-capturable -- no
+ * allocation, no synchronisation, no host read.
+ *
+ * Out of scope: dots fused into the stores of the SpMM or solve kernels,
+ * Gram matrices X^T Y (K x K) and true block CG, other Krylov methods,
+ * distributed plans, the C++ drop-in, the CLI, bench.py. */
+#define SMFV_COL_NEGATE 1   /* s[j] = -s[j] (exact) */
+#define SMFV_COL_ZERO_DEN 2 /* s[j] = +0.0 where den[j] == 0 */
+SMFV_API int smfv_coldot_rule(int *chunk, int *strands);
+SMFV_API int smfv_coldot_workspace_bytes(int m, int K, size_t *bytes);
+SMFV_API int smfv_coldot_host(int m, int K, const double *h_X, int64_t ldx, const double *h_Y, int64_t ldy,
+                              double *h_out);
+SMFV_API int smfv_coldot_f64(int m, int K, const double *d_X, int64_t ldx, const double *d_Y, int64_t ldy,
+                             double *d_out, double *d_workspace, void *stream);
+SMFV_API int smfv_col_axpy_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_X,
+                               int64_t ldx, double *d_Y, int64_t ldy, void *stream);
+SMFV_API int smfv_col_xpay_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_X,
+                               int64_t ldx, double *d_Y, int64_t ldy, void *stream);
+SMFV_API int smfv_pcg_update_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_P,
+                                 int64_t ldp, const double *d_Q, int64_t ldq, double *d_X, int64_t ldx, double *d_R,
+                                 int64_t ldr, double *d_rr, double *d_workspace, void *stream);
+
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,
  * `bytes` (multiple of 16, 16-B aligned pointers) by a 16-byte-per-lane
  * non-temporal copy kernel.  Read + write bytes / time = the measured

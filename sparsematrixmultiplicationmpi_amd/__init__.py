@@ -6,6 +6,7 @@ AlexisBalayre/SparseMatrixMultiplicationMPI).
     T Y = X, T a triangle of A_csr       (level-scheduled solves, sptrsm)
     L U ~ A_csr on A's pattern           (ILU(0), ilu0 / Ilu0Preconditioner)
     B = P A P^T, few levels              (multicolour reordering, DeviceCSR.reordered)
+    d[j] = X[:, j] . Y[:, j], Y += s X   (fixed-order column dots, scaled updates, BlockPCG)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -30,6 +31,7 @@ from .inputs import (  # noqa: F401
     writeMatrixMarketFile,
 )
 from .engine import (  # noqa: F401
+    BlockPCG,
     DeviceCSR,
     Ilu0Plan,
     Ilu0Preconditioner,
@@ -38,10 +40,15 @@ from .engine import (  # noqa: F401
     TrsmPlan,
     VendorSpmm,
     Variant,
+    col_axpy,
+    col_xpay,
+    coldot,
+    coldot_rule,
     compare,
     ilu0,
     ilu0_analyse,
     fill_x_hash,
+    pcg_update,
     sparseMatrixFatVectorMultiply,
     sparseMatrixFatVectorMultiplyColumnWise,
     sparseMatrixFatVectorMultiplyNonZeroElement,

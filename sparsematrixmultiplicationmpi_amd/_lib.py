@@ -89,6 +89,16 @@ _SIGS = {
     "smfv_reorder_plan_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_reorder_plan_stats": (c_int, [c_void_p, _PD]),
     "smfv_reorder_plan_destroy": (c_int, [c_void_p]),
+    "smfv_coldot_rule": (c_int, [_PI, _PI]),
+    "smfv_coldot_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "smfv_coldot_host": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "smfv_coldot_f64": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "smfv_col_axpy_f64": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p]),
+    "smfv_col_xpay_f64": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p]),
+    "smfv_pcg_update_f64": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "smfv_spmm_rowblock_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "smfv_spmm_colpanel_f64": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

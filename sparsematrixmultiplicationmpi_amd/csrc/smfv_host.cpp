@@ -18,6 +18,7 @@
 #include "smfv.h"
 #include "smfv_host.h"
 #include "smfv_internal.h"
+#include "smfv_plan.h"
 
 using smfv::set_error;
 
@@ -771,6 +772,42 @@ SMFV_API int smfv_gen_random_rows(int64_t m, int64_t n, int64_t row_begin, int64
     *out_rp = rp;
     *out_ci = ci;
     *out_va = va;
+    return SMFV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Block vectors: the host half of the column-dot contract (include/smfv.h);
+// the rule and the checks themselves are in smfv_plan.cpp.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+SMFV_API int smfv_coldot_rule(int *chunk, int *strands)
+{
+    SMFV_REQUIRE(chunk && strands, "coldot_rule: null argument");
+    *chunk = smfv::COLDOT_CHUNK;
+    *strands = smfv::COLDOT_STRANDS;
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_coldot_workspace_bytes(int m, int K, size_t *bytes)
+{
+    SMFV_REQUIRE(bytes, "coldot_workspace_bytes: null argument");
+    SMFV_REQUIRE(K >= 1 && m >= 0, "coldot_workspace_bytes: m = %d, K = %d", m, K);
+    *bytes = (size_t)smfv::coldot_chunks(m) * (size_t)K * sizeof(double);
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_coldot_host(int m, int K, const double *h_X, int64_t ldx, const double *h_Y, int64_t ldy, double *h_out)
+{
+    std::string err;
+    // the device entry's checks; the host rule needs no workspace
+    if (!smfv::blockvec_check_coldot(m, K, h_X, ldx, h_Y, ldy, h_out, h_out, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    smfv::coldot_host(m, K, h_X, ldx, h_Y, ldy, h_out);
     return SMFV_OK;
 }
 

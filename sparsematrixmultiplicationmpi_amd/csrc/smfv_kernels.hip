@@ -30,6 +30,10 @@
 //            the lower solve's schedule; no counterpart in the reference
 //   k_permute_rows       fat vectors into another numbering of the rows and
 //            back (smfv_reorder_plan_*); no counterpart in the reference
+//   k_coldot_partial, k_coldot_final, k_col_axpy, k_col_xpay, k_pcg_update
+//            per-column dots in a fixed order and per-column scaled updates of
+//            m x K blocks (smfv_coldot_f64, smfv_col_*_f64,
+//            smfv_pcg_update_f64); no counterpart in the reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -4624,6 +4628,402 @@ SMFV_API int smfv_reorder_plan_destroy(smfv_reorder_plan_t plan)
 {
     delete plan;
     return SMFV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Block vectors (smfv_coldot_f64, smfv_col_axpy_f64, smfv_col_xpay_f64,
+// smfv_pcg_update_f64, include/smfv.h): per-column dots in the fixed order of
+// the column-dot rule, and per-column scaled updates whose scalars are read
+// from device memory by every lane.
+//
+// Lane mapping, as k_permute_rows: a team of TEAM lanes covers the K columns
+// of a row, VEC doubles per lane (VEC = 2: 16-byte accesses, chosen on the
+// host), 256 / TEAM row slots per block, 64-bit element offsets.
+//
+// The chunk kernels (k_coldot_partial, k_pcg_update).  A row slot owns whole
+// strands of a chunk: with RPB = 256 / TEAM >= 32 slots a block works on
+// RPB / 32 chunks at once and slot q owns strand q % 32 of chunk q / 32; with
+// RPB < 32 it works on one chunk and slot q owns the 32 / RPB strands q,
+// q + RPB, ...  A strand's CHUNK / 32 = 16 rows are added in ascending order
+// into one register per column; the rows of UT steps are loaded before the
+// first dependent add.  The tree v[s] += v[s + h], h = 16 .. 1, then runs
+// inside the lane while both strands are its own, by __shfl_down while the
+// two lanes (h * TEAM apart) share a wavefront, and through LDS across
+// wavefronts -- the same five additions per value whatever the mapping.  One
+// plain store per (chunk, column).  k_coldot_final: one lane per column adds
+// the partials in chunk order, 32 loads ahead of the adds.
+//
+// Read-once operands are loaded plain, not non-temporal: inside a solver the
+// next kernel reads the same blocks again and they fit the Infinity Cache
+// (profiles/blockvec/README.md; -DSMFV_BLOCKVEC_NT=1 builds the other form
+// for the A/B).
+// ---------------------------------------------------------------------------
+#ifndef SMFV_BLOCKVEC_NT
+#define SMFV_BLOCKVEC_NT 0
+#endif
+
+namespace smfv {
+
+typedef double bv_d2 __attribute__((ext_vector_type(2)));
+template <int VEC> struct BvT;
+template <> struct BvT<1> {
+    using T = double;
+};
+template <> struct BvT<2> {
+    using T = bv_d2;
+};
+
+template <class T> __device__ __forceinline__ T bv_load(const T *p)
+{
+#if SMFV_BLOCKVEC_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
+__device__ __forceinline__ double bv_zero(double) { return 0.0; }
+__device__ __forceinline__ bv_d2 bv_zero(bv_d2) { return bv_d2{0.0, 0.0}; }
+
+__device__ __forceinline__ double bv_shfl_down(double v, int d) { return __shfl_down(v, d, 64); }
+__device__ __forceinline__ bv_d2 bv_shfl_down(bv_d2 v, int d)
+{
+    return bv_d2{__shfl_down(v.x, d, 64), __shfl_down(v.y, d, 64)};
+}
+
+// s[j] of the scalar rule for one column (include/smfv.h)
+__device__ __forceinline__ double col_scalar1(const double *num, const double *den, int flags, int j)
+{
+    double s = num[j];
+    if (den) {
+        const double d = den[j];
+        s = ((flags & SMFV_COL_ZERO_DEN) && d == 0.0) ? 0.0 : s / d;
+    }
+    return (flags & SMFV_COL_NEGATE) ? -s : s;
+}
+
+template <int VEC>
+__device__ __forceinline__ typename BvT<VEC>::T col_scalar(const double *num, const double *den, int flags, int c)
+{
+    if constexpr (VEC == 2) return bv_d2{col_scalar1(num, den, flags, 2 * c), col_scalar1(num, den, flags, 2 * c + 1)};
+    else return col_scalar1(num, den, flags, c);
+}
+
+constexpr int BV_CHUNK = COLDOT_CHUNK, BV_STRANDS = COLDOT_STRANDS, BV_T = BV_CHUNK / BV_STRANDS;
+static_assert(BV_STRANDS == 32 && BV_CHUNK % BV_STRANDS == 0, "the lane mapping below is written for 32 strands");
+
+// The tree over the 32 strands of a chunk.  acc[u]: this lane's strands
+// q + u * RPB (RPB < 32), or its one strand q % 32.  sh: 256 values of LDS.
+// Returns v[0] in the lanes of strand 0; every lane of the block must call.
+template <int TEAM, class T> __device__ __forceinline__ T strand_tree(T *acc, T *sh)
+{
+    constexpr int RPB = 256 / TEAM, NS = RPB >= 32 ? 1 : 32 / RPB;
+    const int tid = (int)threadIdx.x;
+#pragma unroll
+    for (int h = 16; h >= 1; h >>= 1) {
+        if (h >= RPB) {  // both strands are this lane's
+#pragma unroll
+            for (int u = 0; u < NS; ++u)
+                if (u < h / RPB) acc[u] = acc[u] + acc[u + h / RPB];
+        } else if (h * TEAM < 64) {  // the partner lane is in this wavefront
+            acc[0] = acc[0] + bv_shfl_down(acc[0], h * TEAM);
+        } else {  // across wavefronts
+            sh[tid] = acc[0];
+            __syncthreads();
+            if (tid + h * TEAM < 256) acc[0] = acc[0] + sh[tid + h * TEAM];
+            __syncthreads();
+        }
+    }
+    return acc[0];
+}
+
+// One pass of a block over its chunks.  PCG = false: partials of X . Y (P, Q).
+// PCG = true: X += s P, R += (-s) Q, partials of R . R.  FULL: every row of
+// the block's chunks exists (block-uniform), no per-row condition.
+template <int TEAM, int VEC, bool PCG, bool FULL>
+__device__ __forceinline__ void chunk_body(int m, int K, int nchunks, const double *num, const double *den, int flags,
+                                           const double *P, int64_t ldp, const double *Q, int64_t ldq, double *X,
+                                           int64_t ldx, double *R, int64_t ldr, double *ws,
+                                           typename BvT<VEC>::T *sh)
+{
+    using T = typename BvT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, CPB = RPB >= 32 ? RPB / 32 : 1, NS = RPB >= 32 ? 1 : 32 / RPB;
+    constexpr int UT = PCG ? (NS >= 4 ? 1 : 4 / NS) : (NS >= 8 ? 1 : 8 / NS);  // steps of t loaded together
+    static_assert(BV_T % UT == 0, "UT divides the strand length");
+    const int tl = (int)threadIdx.x & (TEAM - 1), q = (int)threadIdx.x / TEAM;
+    const int chunk = (int)blockIdx.x * CPB + q / 32;
+    const int64_t row0 = (int64_t)chunk * BV_CHUNK + (q & 31);
+    const int nv = K / VEC;  // VEC == 2 only for an even K
+    for (int c0 = 0; c0 < nv; c0 += TEAM) {  // one step unless K > 64 * VEC; block-uniform
+        const int c = c0 + tl;
+        const bool col = c < nv;
+        T s = bv_zero(T{}), ns = bv_zero(T{});
+        if (PCG && col) {
+            s = col_scalar<VEC>(num, den, flags, c);
+            ns = -s;
+        }
+        T acc[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) acc[u] = bv_zero(T{});
+        if (col) {
+#pragma unroll 1  // UT steps in flight, not all sixteen: registers are occupancy
+            for (int t0 = 0; t0 < BV_T; t0 += UT) {
+                T p[UT][NS], qq[UT][NS], x[UT][NS], r[UT][NS];
+                bool ok[UT][NS];
+#pragma unroll
+                for (int a = 0; a < UT; ++a)
+#pragma unroll
+                    for (int u = 0; u < NS; ++u) {
+                        const int64_t row = row0 + (t0 + a) * BV_STRANDS + u * RPB;
+                        ok[a][u] = FULL || row < m;
+                        p[a][u] = qq[a][u] = bv_zero(T{});
+                        if (ok[a][u]) {
+                            p[a][u] = bv_load(reinterpret_cast<const T *>(P + row * ldp) + c);
+                            qq[a][u] = bv_load(reinterpret_cast<const T *>(Q + row * ldq) + c);
+                            if constexpr (PCG) {
+                                x[a][u] = *(reinterpret_cast<const T *>(X + row * ldx) + c);
+                                r[a][u] = *(reinterpret_cast<const T *>(R + row * ldr) + c);
+                            }
+                        }
+                    }
+#pragma unroll
+                for (int a = 0; a < UT; ++a)
+#pragma unroll
+                    for (int u = 0; u < NS; ++u) {
+                        if constexpr (PCG) {
+                            if (ok[a][u]) {
+                                const int64_t row = row0 + (t0 + a) * BV_STRANDS + u * RPB;
+                                const T xn = x[a][u] + s * p[a][u];
+                                const T rn = r[a][u] + ns * qq[a][u];
+                                *(reinterpret_cast<T *>(X + row * ldx) + c) = xn;
+                                *(reinterpret_cast<T *>(R + row * ldr) + c) = rn;
+                                acc[u] = acc[u] + rn * rn;
+                            }
+                        } else {
+                            // a missing row is a product of +0.0: the accumulator cannot be -0.0
+                            acc[u] = acc[u] + p[a][u] * qq[a][u];
+                        }
+                    }
+            }
+        }
+        const T v = strand_tree<TEAM, T>(acc, sh);
+        if (col && (q & 31) == 0 && chunk < nchunks) reinterpret_cast<T *>(ws + (int64_t)chunk * K)[c] = v;
+    }
+}
+
+// nchunks = max(1, chunks of m): for m = 0 chunk 0 is written as +0.0
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(256) void k_coldot_partial(int m, int K, int nchunks, const double *X, int64_t ldx,
+                                                        const double *Y, int64_t ldy, double *ws)
+{
+    using T = typename BvT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, CPB = RPB >= 32 ? RPB / 32 : 1;
+    __shared__ T sh[256];
+    if (((int64_t)blockIdx.x + 1) * CPB * BV_CHUNK <= m)
+        chunk_body<TEAM, VEC, false, true>(m, K, nchunks, nullptr, nullptr, 0, X, ldx, Y, ldy, nullptr, 0, nullptr, 0, ws, sh);
+    else
+        chunk_body<TEAM, VEC, false, false>(m, K, nchunks, nullptr, nullptr, 0, X, ldx, Y, ldy, nullptr, 0, nullptr, 0, ws, sh);
+}
+
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(256) void k_pcg_update(int m, int K, int nchunks, const double *__restrict__ num,
+                                                    const double *__restrict__ den, int flags,
+                                                    const double *__restrict__ P, int64_t ldp,
+                                                    const double *__restrict__ Q, int64_t ldq, double *__restrict__ X,
+                                                    int64_t ldx, double *__restrict__ R, int64_t ldr,
+                                                    double *__restrict__ ws)
+{
+    using T = typename BvT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, CPB = RPB >= 32 ? RPB / 32 : 1;
+    __shared__ T sh[256];
+    if (((int64_t)blockIdx.x + 1) * CPB * BV_CHUNK <= m)
+        chunk_body<TEAM, VEC, true, true>(m, K, nchunks, num, den, flags, P, ldp, Q, ldq, X, ldx, R, ldr, ws, sh);
+    else
+        chunk_body<TEAM, VEC, true, false>(m, K, nchunks, num, den, flags, P, ldp, Q, ldq, X, ldx, R, ldr, ws, sh);
+}
+
+// out[j] = ((+0.0 + ws[0, j]) + ws[1, j]) + ...: one lane per column
+__global__ __launch_bounds__(256) void k_coldot_final(int nchunks, int K, const double *__restrict__ ws,
+                                                      double *__restrict__ out)
+{
+    constexpr int B = 32;  // a batch costs one memory latency whatever its size; 64 would spill SGPRs
+    const int j = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (j >= K) return;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < nchunks; c0 += B) {
+        double v[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) v[u] = c0 + u < nchunks ? ws[(int64_t)(c0 + u) * K + j] : 0.0;
+#pragma unroll
+        for (int u = 0; u < B; ++u) acc = acc + v[u];  // + (+0.0) past the end changes nothing
+    }
+    out[j] = acc;
+}
+
+// Y = Y + s X (XPAY = false) or Y = X + s Y (XPAY = true), R = 4 rows in
+// flight per team.  Y carries no __restrict__ against X: in place is legal.
+template <int TEAM, int VEC, bool XPAY, bool FULL>
+__device__ __forceinline__ void col_update_body(int m, int K, const double *num, const double *den, int flags,
+                                                const double *X, int64_t ldx, double *Y, int64_t ldy, int64_t r0)
+{
+    using T = typename BvT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, R = 4;
+    const int tl = (int)threadIdx.x & (TEAM - 1);
+    const int nv = K / VEC;
+    for (int c = tl; c < nv; c += TEAM) {
+        const T s = col_scalar<VEC>(num, den, flags, c);
+        T x[R], y[R];
+        bool ok[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int64_t row = r0 + u * RPB;
+            ok[u] = FULL || row < m;
+            if (ok[u]) {
+                x[u] = bv_load(reinterpret_cast<const T *>(X + row * ldx) + c);
+                y[u] = *(reinterpret_cast<const T *>(Y + row * ldy) + c);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u)
+            if (ok[u]) {
+                const int64_t row = r0 + u * RPB;
+                *(reinterpret_cast<T *>(Y + row * ldy) + c) = XPAY ? x[u] + s * y[u] : y[u] + s * x[u];
+            }
+    }
+}
+
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(256) void k_col_axpy(int m, int K, const double *num, const double *den, int flags,
+                                                  const double *X, int64_t ldx, double *Y, int64_t ldy)
+{
+    constexpr int RPB = 256 / TEAM, R = 4;
+    const int64_t b0 = (int64_t)blockIdx.x * (RPB * R), r0 = b0 + (int)threadIdx.x / TEAM;
+    if (b0 + RPB * R <= m) col_update_body<TEAM, VEC, false, true>(m, K, num, den, flags, X, ldx, Y, ldy, r0);
+    else col_update_body<TEAM, VEC, false, false>(m, K, num, den, flags, X, ldx, Y, ldy, r0);
+}
+
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(256) void k_col_xpay(int m, int K, const double *num, const double *den, int flags,
+                                                  const double *X, int64_t ldx, double *Y, int64_t ldy)
+{
+    constexpr int RPB = 256 / TEAM, R = 4;
+    const int64_t b0 = (int64_t)blockIdx.x * (RPB * R), r0 = b0 + (int)threadIdx.x / TEAM;
+    if (b0 + RPB * R <= m) col_update_body<TEAM, VEC, true, true>(m, K, num, den, flags, X, ldx, Y, ldy, r0);
+    else col_update_body<TEAM, VEC, true, false>(m, K, num, den, flags, X, ldx, Y, ldy, r0);
+}
+
+}  // namespace smfv
+
+namespace {
+
+// the chunk kernels' geometry for (team): chunks per block
+int bv_chunks_per_block(int team) { return 256 / team >= 32 ? 256 / team / 32 : 1; }
+
+int bv_pick_vec4(const double *A, int64_t lda, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D,
+                 int64_t ldd, int K)
+{
+    return (pick_vec(A, lda, B, ldb, K) == 2 && pick_vec(C, ldc, D, ldd, K) == 2) ? 2 : 1;
+}
+
+int coldot_final_launch(int nchunks, int K, const double *ws, double *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_coldot_final, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, nchunks, K, ws, out);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+template <bool XPAY>
+int col_update_launch(int m, int K, const double *num, const double *den, int flags, const double *X, int64_t ldx, double *Y,
+                      int64_t ldy, hipStream_t st)
+{
+    if (m == 0) return SMFV_OK;
+    const int vec = pick_vec(X, ldx, Y, ldy, K);
+    const int team = pick_team(K, vec);
+    const int rows_per_block = 256 / team * 4;
+    const unsigned nblk = (unsigned)(((int64_t)m + rows_per_block - 1) / rows_per_block);
+    if constexpr (XPAY) {
+#define LX(T_, V_) hipLaunchKernelGGL((k_col_xpay<T_, V_>), dim3(nblk), dim3(256), 0, st, m, K, num, den, flags, X, ldx, Y, ldy)
+        SMFV_TEAM_SWITCH(team, vec, LX)
+#undef LX
+    } else {
+#define LA(T_, V_) hipLaunchKernelGGL((k_col_axpy<T_, V_>), dim3(nblk), dim3(256), 0, st, m, K, num, den, flags, X, ldx, Y, ldy)
+        SMFV_TEAM_SWITCH(team, vec, LA)
+#undef LA
+    }
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+SMFV_API int smfv_coldot_f64(int m, int K, const double *d_X, int64_t ldx, const double *d_Y, int64_t ldy, double *d_out,
+                             double *d_workspace, void *stream)
+{
+    std::string err;
+    if (!blockvec_check_coldot(m, K, d_X, ldx, d_Y, ldy, d_out, d_workspace, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const int nchunks = (int)coldot_chunks(m);
+    // the partials are stored two at a time too
+    const int vec = aligned16(d_workspace) ? pick_vec(d_X, ldx, d_Y, ldy, K) : 1;
+    const int team = pick_team(K, vec);
+    const int cpb = bv_chunks_per_block(team);
+    const unsigned nblk = (unsigned)((nchunks + cpb - 1) / cpb);
+#define LD(T_, V_) hipLaunchKernelGGL((k_coldot_partial<T_, V_>), dim3(nblk), dim3(256), 0, st, m, K, nchunks, d_X, ldx, d_Y, ldy, d_workspace)
+    SMFV_TEAM_SWITCH(team, vec, LD)
+#undef LD
+    SMFV_LAUNCHED();
+    return coldot_final_launch(nchunks, K, d_workspace, d_out, st);
+}
+
+SMFV_API int smfv_col_axpy_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_X,
+                               int64_t ldx, double *d_Y, int64_t ldy, void *stream)
+{
+    std::string err;
+    if (!blockvec_check_update("col_axpy", m, K, d_num, flags, d_X, ldx, d_Y, ldy, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return col_update_launch<false>(m, K, d_num, d_den, flags, d_X, ldx, d_Y, ldy, as_stream(stream));
+}
+
+SMFV_API int smfv_col_xpay_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_X,
+                               int64_t ldx, double *d_Y, int64_t ldy, void *stream)
+{
+    std::string err;
+    if (!blockvec_check_update("col_xpay", m, K, d_num, flags, d_X, ldx, d_Y, ldy, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    return col_update_launch<true>(m, K, d_num, d_den, flags, d_X, ldx, d_Y, ldy, as_stream(stream));
+}
+
+SMFV_API int smfv_pcg_update_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_P,
+                                 int64_t ldp, const double *d_Q, int64_t ldq, double *d_X, int64_t ldx, double *d_R,
+                                 int64_t ldr, double *d_rr, double *d_workspace, void *stream)
+{
+    std::string err;
+    if (!blockvec_check_pcg_update(m, K, d_num, flags, d_P, ldp, d_Q, ldq, d_X, ldx, d_R, ldr, d_rr, d_workspace, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const int nchunks = (int)coldot_chunks(m);
+    const int vec = aligned16(d_workspace) ? bv_pick_vec4(d_P, ldp, d_Q, ldq, d_X, ldx, d_R, ldr, K) : 1;
+    const int team = pick_team(K, vec);
+    const int cpb = bv_chunks_per_block(team);
+    const unsigned nblk = (unsigned)((nchunks + cpb - 1) / cpb);
+#define LU(T_, V_) hipLaunchKernelGGL((k_pcg_update<T_, V_>), dim3(nblk), dim3(256), 0, st, m, K, nchunks, d_num, d_den, flags, d_P, ldp, d_Q, ldq, d_X, ldx, d_R, ldr, d_workspace)
+    SMFV_TEAM_SWITCH(team, vec, LU)
+#undef LU
+    SMFV_LAUNCHED();
+    return coldot_final_launch(nchunks, K, d_workspace, d_rr, st);
 }
 
 }  // extern "C"

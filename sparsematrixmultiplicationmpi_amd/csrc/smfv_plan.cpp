@@ -2254,4 +2254,108 @@ bool csr_permute_sym(int m, const int *rp, const int *ci, const int *perm, int *
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Block vectors: the column-dot rule on the host and the argument checks
+// (smfv_plan.h).
+// ---------------------------------------------------------------------------
+void coldot_host(int m, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, double *out)
+{
+    static_assert(COLDOT_CHUNK % COLDOT_STRANDS == 0 && (COLDOT_STRANDS & (COLDOT_STRANDS - 1)) == 0, "the rule's constants");
+    for (int j = 0; j < K; ++j) {
+        double d = 0.0;
+        for (int64_t c0 = 0; c0 < m; c0 += COLDOT_CHUNK) {
+            const int64_t end = std::min<int64_t>(m, c0 + COLDOT_CHUNK);
+            double v[COLDOT_STRANDS];
+            for (int s = 0; s < COLDOT_STRANDS; ++s) {
+                double a = 0.0;
+                for (int64_t r = c0 + s; r < end; r += COLDOT_STRANDS) a = a + X[r * ldx + j] * Y[r * ldy + j];
+                v[s] = a;
+            }
+            for (int h = COLDOT_STRANDS / 2; h >= 1; h /= 2)
+                for (int s = 0; s < h; ++s) v[s] = v[s] + v[s + h];
+            d = d + v[0];
+        }
+        out[j] = d;
+    }
+}
+
+namespace {
+
+bool blockvec_fail(std::string *err, const char *name, const char *what)
+{
+    if (err) *err = std::string(name) + ": " + what;
+    return false;
+}
+
+bool blockvec_sizes(const char *name, int m, int K, std::string *err)
+{
+    if (K < 1) return blockvec_fail(err, name, ("K = " + std::to_string(K) + ", must be at least 1").c_str());
+    if (m < 0) return blockvec_fail(err, name, ("m = " + std::to_string(m) + ", must not be negative").c_str());
+    return true;
+}
+
+bool blockvec_block(const char *name, const char *which, int m, int K, const void *p, int64_t ld, std::string *err)
+{
+    if (ld < K) return blockvec_fail(err, name, (std::string("leading dimension of ") + which + " smaller than K").c_str());
+    if (m > 0 && !p) return blockvec_fail(err, name, (std::string("null ") + which).c_str());
+    return true;
+}
+
+// do the m x K windows (a, lda) and (b, ldb) share an element?
+bool blocks_meet(int m, int K, const void *a, int64_t lda, const void *b, int64_t ldb)
+{
+    if (m == 0) return false;
+    const int64_t pa = (int64_t)(reinterpret_cast<uintptr_t>(a)), pb = (int64_t)(reinterpret_cast<uintptr_t>(b));
+    const int64_t ea = pa + 8 * ((int64_t)(m - 1) * lda + K), eb = pb + 8 * ((int64_t)(m - 1) * ldb + K);
+    if (ea <= pb || eb <= pa) return false;  // the byte ranges do not meet
+    const int64_t d = pa > pb ? pa - pb : pb - pa;
+    if (lda != ldb || d % 8 != 0) return true;  // interleaved in no simple way: refused
+    const int64_t r = (d / 8) % lda;            // column shift of one window against the other
+    return r < K || lda - r < K;
+}
+
+}  // namespace
+
+bool blockvec_check_coldot(int m, int K, const void *X, int64_t ldx, const void *Y, int64_t ldy, const void *out,
+                           const void *ws, std::string *err)
+{
+    const char *name = "coldot";
+    if (!blockvec_sizes(name, m, K, err)) return false;
+    if (!blockvec_block(name, "X", m, K, X, ldx, err) || !blockvec_block(name, "Y", m, K, Y, ldy, err)) return false;
+    if (!out) return blockvec_fail(err, name, "null out");
+    if (!ws) return blockvec_fail(err, name, "null workspace");
+    return true;
+}
+
+bool blockvec_check_update(const char *name, int m, int K, const void *num, int flags, const void *X, int64_t ldx,
+                           const void *Y, int64_t ldy, std::string *err)
+{
+    if (!blockvec_sizes(name, m, K, err)) return false;
+    if (flags & ~COL_FLAGS) return blockvec_fail(err, name, ("unknown flags " + std::to_string(flags)).c_str());
+    if (!num) return blockvec_fail(err, name, "null num");
+    return blockvec_block(name, "X", m, K, X, ldx, err) && blockvec_block(name, "Y", m, K, Y, ldy, err);
+}
+
+bool blockvec_check_pcg_update(int m, int K, const void *num, int flags, const void *P, int64_t ldp, const void *Q,
+                               int64_t ldq, const void *X, int64_t ldx, const void *R, int64_t ldr, const void *rr,
+                               const void *ws, std::string *err)
+{
+    const char *name = "pcg_update";
+    if (!blockvec_sizes(name, m, K, err)) return false;
+    if (flags & ~COL_FLAGS) return blockvec_fail(err, name, ("unknown flags " + std::to_string(flags)).c_str());
+    if (!num) return blockvec_fail(err, name, "null num");
+    const void *blk[4] = {P, Q, X, R};
+    const int64_t ld[4] = {ldp, ldq, ldx, ldr};
+    const char *nm[4] = {"P", "Q", "X", "R"};
+    for (int i = 0; i < 4; ++i)
+        if (!blockvec_block(name, nm[i], m, K, blk[i], ld[i], err)) return false;
+    if (!rr) return blockvec_fail(err, name, "null rr");
+    if (!ws) return blockvec_fail(err, name, "null workspace");
+    for (int i = 0; i < 4; ++i)
+        for (int k = i + 1; k < 4; ++k)
+            if (blocks_meet(m, K, blk[i], ld[i], blk[k], ld[k]))
+                return blockvec_fail(err, name, (std::string(nm[i]) + " and " + nm[k] + " overlap").c_str());
+    return true;
+}
+
 }  // namespace smfv

@@ -492,4 +492,33 @@ bool check_permutation(int64_t m, const int *perm, int *inv, const char *what, s
 bool csr_permute_sym(int m, const int *row_ptr, const int *col_idx, const int *perm, int *b_row_ptr, int *b_col_idx,
                      int *b_vperm, std::string *err);
 
+// ---------------------------------------------------------------------------
+// Block vectors (smfv_coldot_*, smfv_col_axpy_f64, smfv_col_xpay_f64,
+// smfv_pcg_update_f64, include/smfv.h): the two constants of the column-dot
+// rule, the rule itself on the host, and the argument checks every device
+// entry runs before its first device call.  Host only.
+// ---------------------------------------------------------------------------
+constexpr int COLDOT_CHUNK = 512;   // rows per chunk
+constexpr int COLDOT_STRANDS = 32;  // interleaved accumulators per chunk; a power of two dividing COLDOT_CHUNK
+constexpr int COL_FLAGS = 1 | 2;    // SMFV_COL_NEGATE | SMFV_COL_ZERO_DEN
+
+// max(1, chunks of m rows): the partials per column, and the workspace rows
+inline int64_t coldot_chunks(int64_t m) { return m <= 0 ? 1 : (m + COLDOT_CHUNK - 1) / COLDOT_CHUNK; }
+
+// The column-dot rule in plain C++: out[j], j in [0, K).  X may be Y.
+void coldot_host(int m, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, double *out);
+
+// false (with *err) for K < 1, m < 0, a leading dimension below K, a NULL
+// out / workspace / num, a NULL block with m > 0, unknown flags; `name` starts
+// the message.
+bool blockvec_check_coldot(int m, int K, const void *X, int64_t ldx, const void *Y, int64_t ldy, const void *out,
+                           const void *ws, std::string *err);
+bool blockvec_check_update(const char *name, int m, int K, const void *num, int flags, const void *X, int64_t ldx,
+                           const void *Y, int64_t ldy, std::string *err);
+// ... and any two of P, Q, X, R sharing an element: their byte ranges meet
+// and they are not disjoint column windows of one leading dimension.
+bool blockvec_check_pcg_update(int m, int K, const void *num, int flags, const void *P, int64_t ldp, const void *Q,
+                               int64_t ldq, const void *X, int64_t ldx, const void *R, int64_t ldr, const void *rr,
+                               const void *ws, std::string *err);
+
 }  // namespace smfv

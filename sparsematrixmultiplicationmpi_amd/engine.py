@@ -667,6 +667,294 @@ class Ilu0Preconditioner:
         return self.R.to_old(W, Y, stream)
 
 
+COL_NEGATE, COL_ZERO_DEN = 1, 2  # SMFV_COL_*
+
+
+def coldot_rule() -> tuple[int, int]:
+    """(CHUNK, STRANDS) of the column-dot rule (smfv_coldot_rule)."""
+    chunk, strands = ctypes.c_int(0), ctypes.c_int(0)
+    call("smfv_coldot_rule", byref(chunk), byref(strands))
+    return chunk.value, strands.value
+
+
+def coldot_workspace_doubles(m: int, K: int) -> int:
+    b = c_size_t(0)
+    call("smfv_coldot_workspace_bytes", int(m), int(K), byref(b))
+    return b.value // 8
+
+
+def _block_shape(X: torch.Tensor, name: str) -> tuple[int, int]:
+    if X.dim() != 2 or X.shape[1] < 1:
+        raise ValueError(f"{name} must have shape (m, K) with K >= 1, got {tuple(X.shape)}")
+    return int(X.shape[0]), int(X.shape[1])
+
+
+def _check_cols(v: torch.Tensor | None, K: int, name: str, like: torch.Tensor) -> int:
+    """A per-column array: K contiguous float64 entries on `like`'s device; its address (0 for None)."""
+    if v is None:
+        return 0
+    if not v.is_cuda or v.dtype != torch.float64 or v.device != like.device:
+        raise TypeError(f"{name} must be a float64 HIP tensor on {like.device}")
+    if v.dim() != 1 or v.shape[0] != K or (K > 1 and v.stride(0) != 1):
+        raise ValueError(f"{name} must be {K} contiguous entries, got shape {tuple(v.shape)}")
+    return v.data_ptr()
+
+
+def _same_device(X: torch.Tensor, Y: torch.Tensor, name: str) -> None:
+    if Y.device != X.device:
+        raise TypeError(f"{name} is on {Y.device}, not on {X.device}")
+
+
+def coldot(X: torch.Tensor, Y: torch.Tensor, out: torch.Tensor | None = None,
+           stream: torch.cuda.Stream | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """out[j] = sum_i X[i, j] * Y[i, j] in the fixed order of the column-dot
+    rule (include/smfv.h; smfv_coldot_f64), asynchronous on `stream`.  X may
+    be Y.  Without `out` / `workspace` (coldot_workspace_doubles entries) they
+    are allocated here; a caller that captures passes both."""
+    m, K = _block_shape(X, "X")
+    ldx = _check_dense(X, m, K, "X")
+    ldy = _check_dense(Y, m, K, "Y")
+    _same_device(X, Y, "Y")
+    if out is None:
+        out = torch.empty(K, dtype=torch.float64, device=X.device)
+    if workspace is None:
+        workspace = torch.empty(coldot_workspace_doubles(m, K), dtype=torch.float64, device=X.device)
+    elif not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous() \
+            or workspace.numel() < coldot_workspace_doubles(m, K):
+        raise ValueError(f"workspace must be a contiguous float64 HIP tensor of {coldot_workspace_doubles(m, K)} entries")
+    call("smfv_coldot_f64", m, K, X.data_ptr(), ldx, Y.data_ptr(), ldy, _check_cols(out, K, "out", X),
+         workspace.data_ptr(), stream_handle(stream))
+    return out
+
+
+def _col_flags(negate: bool, zero_den: bool) -> int:
+    return (COL_NEGATE if negate else 0) | (COL_ZERO_DEN if zero_den else 0)
+
+
+def _col_update(fn: str, num, den, X, Y, negate, zero_den, stream) -> torch.Tensor:
+    m, K = _block_shape(X, "X")
+    ldx = _check_dense(X, m, K, "X")
+    ldy = _check_dense(Y, m, K, "Y")
+    _same_device(X, Y, "Y")
+    if num is None:
+        raise TypeError("num must be a tensor of K entries")
+    call(fn, m, K, _check_cols(num, K, "num", X), _check_cols(den, K, "den", X), _col_flags(negate, zero_den),
+         X.data_ptr(), ldx, Y.data_ptr(), ldy, stream_handle(stream))
+    return Y
+
+
+def col_axpy(num: torch.Tensor, den: torch.Tensor | None, X: torch.Tensor, Y: torch.Tensor, negate: bool = False,
+             zero_den: bool = False, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Y[:, j] += s[j] * X[:, j] with s = num / den (den None: s = num) formed
+    on the device (smfv_col_axpy_f64); negate flips s, zero_den makes s[j]
+    +0.0 where den[j] == 0.  Y may be X."""
+    return _col_update("smfv_col_axpy_f64", num, den, X, Y, negate, zero_den, stream)
+
+
+def col_xpay(num: torch.Tensor, den: torch.Tensor | None, X: torch.Tensor, Y: torch.Tensor, negate: bool = False,
+             zero_den: bool = False, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Y[:, j] = X[:, j] + s[j] * Y[:, j] (smfv_col_xpay_f64); s as in col_axpy."""
+    return _col_update("smfv_col_xpay_f64", num, den, X, Y, negate, zero_den, stream)
+
+
+def pcg_update(num: torch.Tensor, den: torch.Tensor | None, P: torch.Tensor, Q: torch.Tensor, X: torch.Tensor,
+               R: torch.Tensor, rr: torch.Tensor | None = None, negate: bool = False, zero_den: bool = False,
+               stream: torch.cuda.Stream | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """X += s P, R -= s Q and rr = coldot(R, R) of the new R in one pass
+    (smfv_pcg_update_f64), bit-identical to the three separate calls.  The
+    four blocks must not overlap.  Returns rr."""
+    m, K = _block_shape(X, "X")
+    lds = [_check_dense(T, m, K, n) for T, n in ((P, "P"), (Q, "Q"), (X, "X"), (R, "R"))]
+    for T, n in ((P, "P"), (Q, "Q"), (R, "R")):
+        _same_device(X, T, n)
+    if num is None:
+        raise TypeError("num must be a tensor of K entries")
+    if rr is None:
+        rr = torch.empty(K, dtype=torch.float64, device=X.device)
+    if workspace is None:
+        workspace = torch.empty(coldot_workspace_doubles(m, K), dtype=torch.float64, device=X.device)
+    elif not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous() \
+            or workspace.numel() < coldot_workspace_doubles(m, K):
+        raise ValueError(f"workspace must be a contiguous float64 HIP tensor of {coldot_workspace_doubles(m, K)} entries")
+    call("smfv_pcg_update_f64", m, K, _check_cols(num, K, "num", X), _check_cols(den, K, "den", X),
+         _col_flags(negate, zero_den), P.data_ptr(), lds[0], Q.data_ptr(), lds[1], X.data_ptr(), lds[2], R.data_ptr(),
+         lds[3], _check_cols(rr, K, "rr", X), workspace.data_ptr(), stream_handle(stream))
+    return rr
+
+
+class BlockPCG:
+    """Preconditioned conjugate gradients on K right-hand sides at once, every
+    column a CG of its own (no Gram matrices): A X = B for a symmetric
+    positive definite A.
+
+    A: a DeviceCSR (a ROWWISE SpmmPlan is made) or a non-transposed SpmmPlan
+    of the caller's.  M: anything with apply(X, Y, stream=...) computing
+    Y = M^-1 X -- an Ilu0Preconditioner in either ordering --, or None for the
+    identity: Z is R then, nothing is copied, and rz is rr (one dot fewer).
+    Every block (X, R, P, Q, Z), the per-column scalars and the dot workspace
+    are allocated here, once.
+
+    An iteration is Q = A P; pq = coldot(P, Q); the fused update with
+    s = rz / pq, which also gives rr; Z = M(R); rz' = coldot(R, Z);
+    P = Z + (rz' / rz) P; rz <- rz'.  The quotients are formed on the device
+    with the zero-denominator guard always on, so a column whose residual is
+    exactly zero stays exactly where it is; converged columns keep iterating.
+    iterate() makes no host read, allocation or synchronisation and captures
+    into a graph.  rz and rz' swap buffers every iteration: capture an EVEN
+    number of iterations, so that a replay starts where the capture did
+    (solve(graph=True) keeps one graph per parity instead)."""
+
+    def __init__(self, A, K: int, M=None, stream: torch.cuda.Stream | None = None):
+        if isinstance(A, SpmmPlan):
+            if A._transposed or A.rows is not None:
+                raise ValueError("BlockPCG needs a plan of the whole A, not a transposed or a row-block plan")
+            if A.K != int(K):
+                raise ValueError(f"the plan was made for K = {A.K}, not {K}")
+            self.plan, self.A = A, A.A
+        elif isinstance(A, DeviceCSR):
+            self.plan, self.A = SpmmPlan(Variant.ROWWISE, A, int(K), stream=stream), A
+        else:
+            raise TypeError("A must be a DeviceCSR or an SpmmPlan")
+        if self.A.m != self.A.n:
+            raise ValueError(f"BlockPCG needs a square matrix, got {self.A.m} x {self.A.n}")
+        if M is not None and not callable(getattr(M, "apply", None)):
+            raise TypeError("M must have apply(X, Y, stream=...) or be None")
+        self.K, self.M, self.stream = int(K), M, stream
+        m, dev = self.A.m, self.A.device
+        new = lambda: torch.zeros((m, self.K), dtype=torch.float64, device=dev)  # noqa: E731
+        self.X, self.R, self.P, self.Q = new(), new(), new(), new()
+        self.Z = self.R if M is None else new()
+        # rows: rz (even iterations), bb, rz (odd), pq, rr, bb again.  With M,
+        # (rr, bb) are rows 4:6; without, rr is the current rz beside row 1.
+        self._sc = torch.zeros((6, self.K), dtype=torch.float64, device=dev)
+        self._one = torch.ones(self.K, dtype=torch.float64, device=dev)
+        self._ws = torch.empty(coldot_workspace_doubles(m, self.K), dtype=torch.float64, device=dev)
+        self._host = torch.empty((2, self.K), dtype=torch.float64).pin_memory()
+        self._par = 0  # which of rows 0 / 2 holds rz
+        self._graphs = None
+        self.iterations = 0
+
+    def _rz(self, par: int) -> torch.Tensor:
+        return self._sc[2 * par]
+
+    @property
+    def rr(self) -> torch.Tensor:
+        """R . R per column after the last iteration (on the device)."""
+        return self._sc[4] if self.M is not None else self._rz(self._par)
+
+    @property
+    def bb(self) -> torch.Tensor:
+        """B . B per column of the last start() (on the device)."""
+        return self._sc[1]
+
+    def start(self, B: torch.Tensor, X0: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> None:
+        """R = B - A X0 (X0 None: X = 0, R = B, A is not launched), Z = M(R),
+        P = Z, rz = coldot(R, Z), bb = coldot(B, B); asynchronous."""
+        s = stream if stream is not None else self.stream
+        m, K = self.A.m, self.K
+        _check_dense(B, m, K, "B")
+        with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+            self.R.copy_(B)
+            if X0 is None:
+                self.X.zero_()
+            else:
+                _check_dense(X0, m, K, "X0")
+                self.X.copy_(X0)
+                self.plan.run(self.X, self.Q, s)
+                col_axpy(self._one, None, self.Q, self.R, negate=True, stream=s)  # R = B - A X0
+            if self.M is not None:
+                self.M.apply(self.R, self.Z, stream=s)
+            self.P.copy_(self.Z)
+            self._par = 0
+            coldot(self.R, self.Z, self._rz(0), s, self._ws)
+            coldot(B, B, self._sc[1], s, self._ws)
+            self._sc[5].copy_(self._sc[1])
+        self.iterations = 0
+
+    def iterate(self, n: int = 1, stream: torch.cuda.Stream | None = None) -> None:
+        """n iterations, launched back to back on `stream`: no host read, no
+        allocation, no synchronisation."""
+        s = stream if stream is not None else self.stream
+        for _ in range(int(n)):
+            rz, rz_new, pq = self._rz(self._par), self._rz(1 - self._par), self._sc[3]
+            self.plan.run(self.P, self.Q, s)
+            coldot(self.P, self.Q, pq, s, self._ws)
+            if self.M is None:  # Z is R and rz' is rr
+                pcg_update(rz, pq, self.P, self.Q, self.X, self.R, rz_new, zero_den=True, stream=s, workspace=self._ws)
+            else:
+                pcg_update(rz, pq, self.P, self.Q, self.X, self.R, self._sc[4], zero_den=True, stream=s,
+                           workspace=self._ws)
+                self.M.apply(self.R, self.Z, stream=s)
+                coldot(self.R, self.Z, rz_new, s, self._ws)
+            col_xpay(rz_new, rz, self.Z, self.P, zero_den=True, stream=s)
+            self._par = 1 - self._par
+        self.iterations += int(n)
+
+    def residuals(self, stream: torch.cuda.Stream | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """(rr, bb) on the host: one read of 2 K doubles, then a wait for it."""
+        s = stream if stream is not None else self.stream
+        if self.M is not None:
+            src, swap = self._sc[4:6], False
+        else:  # rr is the current rz: rows (0, 1) or (1, 2)
+            src, swap = (self._sc[0:2], False) if self._par == 0 else (self._sc[1:3], True)
+        with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+            self._host.copy_(src, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        h = self._host.numpy().copy()
+        return (h[1], h[0]) if swap else (h[0], h[1])
+
+    def _capture(self, s) -> None:
+        """One graph per parity of the rz buffers, each of one iteration."""
+        side = s if s is not None else torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        par, its = self._par, self.iterations
+        self._graphs = {}
+        for p in (par, 1 - par):
+            g = torch.cuda.CUDAGraph()
+            assert self._par == p
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    self.iterate(1, side)
+            self._graphs[p] = g
+        self._par, self.iterations = par, its  # a capture executes nothing
+        torch.cuda.current_stream().wait_stream(side)
+
+    def solve(self, B: torch.Tensor, X0: torch.Tensor | None = None, tol: float = 1e-8, max_iters: int = 1000,
+              check_every: int = 1, graph: bool = False):
+        """Iterates until every column has rr[j] <= (tol * tol) * bb[j]
+        (evaluated in fp64 on the host from one read of 2 K doubles every
+        `check_every` iterations) or max_iters is reached.  graph: replay
+        captured iterations instead of launching them.  Returns (X, the
+        iteration count, rr / bb per column as a numpy array; 0 for a zero
+        right-hand side met exactly)."""
+        if check_every < 1 or max_iters < 0:
+            raise ValueError("check_every must be at least 1 and max_iters non-negative")
+        s = self.stream
+        self.start(B, X0, s)
+        if graph and self._graphs is None:
+            self._capture(s)
+        rr = bb = None
+        while self.iterations < max_iters:
+            n = min(int(check_every), max_iters - self.iterations)
+            if graph:
+                with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+                    for _ in range(n):
+                        self._graphs[self._par].replay()
+                        self._par = 1 - self._par
+                self.iterations += n
+            else:
+                self.iterate(n, s)
+            rr, bb = self.residuals(s)
+            if bool(np.all(rr <= (tol * tol) * bb)):
+                break
+        if rr is None:
+            rel = np.full(self.K, np.nan)
+        else:
+            with np.errstate(all="ignore"):
+                rel = np.where(bb == 0.0, np.where(rr == 0.0, 0.0, np.inf), rr / bb)
+        return self.X, self.iterations, rel
+
+
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,
                   stream=None) -> torch.Tensor:
     K = X.shape[1]
