@@ -777,8 +777,8 @@ SMFV_API int smfv_reorder_plan_destroy(smfv_reorder_plan_t plan);
  * allocation, no synchronisation, no host read.
  *
  * Out of scope: dots fused into the stores of the SpMM or solve kernels,
- * Gram matrices X^T Y (K x K) and true block CG, other Krylov methods,
- * distributed plans, the C++ drop-in, the CLI, bench.py. */
+ * other Krylov methods (Gram matrices X^T Y and a coupled block CG: the next
+ * section), distributed plans, the C++ drop-in, the CLI, bench.py. */
 #define SMFV_COL_NEGATE 1   /* s[j] = -s[j] (exact) */
 #define SMFV_COL_ZERO_DEN 2 /* s[j] = +0.0 where den[j] == 0 */
 SMFV_API int smfv_coldot_rule(int *chunk, int *strands);
@@ -794,6 +794,97 @@ SMFV_API int smfv_col_xpay_f64(int m, int K, const double *d_num, const double *
 SMFV_API int smfv_pcg_update_f64(int m, int K, const double *d_num, const double *d_den, int flags, const double *d_P,
                                  int64_t ldp, const double *d_Q, int64_t ldq, double *d_X, int64_t ldx, double *d_R,
                                  int64_t ldr, double *d_rr, double *d_workspace, void *stream);
+
+/* ---- Coupled blocks: Gram matrices, block . matrix updates, small solves ----
+ * What a true block Krylov method needs on top of the block-vector family: the
+ * K x K Gram matrix of two blocks, the update of a block by another block
+ * times a small matrix, and the solution of a small dense system, all on the
+ * device, so that a coupled block PCG iteration makes no host read and
+ * captures into a graph.  fp64, row-major with leading dimensions, never an
+ * FMA (-ffp-contract=off: every product and sum is rounded on its own), no
+ * atomics, flags, spinning or cooperative launch, a fixed launch sequence.
+ *
+ * smfv_gram_f64: G = X^T Y.  X is m x Kx, Y is m x Ky, G is Kx x Ky with
+ *   ldg >= Ky, Kx and Ky each in 1..128; X may be Y.  G[i,j] is the
+ *   column-dot rule of the block-vector section applied, with nothing changed,
+ *   to column i of X and column j of Y: chunks of CHUNK = 512 rows,
+ *   STRANDS = 32 interleaved accumulators from +0.0 adding fl(x * y) in
+ *   ascending row order, the shuffle-down tree h = 16, 8, 4, 2, 1, the chunk
+ *   partials added in ascending chunk order from +0.0.  So
+ *   gram(X, Y)[i,j] == coldot(X[:,i], Y[:,j]) bit for bit, diag(gram(R, R))
+ *   is coldot(R, R), no entry is ever -0.0, NaN in gives NaN out, m = 0 gives
+ *   +0.0, and the result depends on (m, Kx, Ky, the data) only -- not on the
+ *   grid, the tiling of G, the access width or the alignment path.
+ *   On the device: k_gram_partial writes one Kx x Ky partial per chunk into
+ *   the caller's workspace (smfv_gram_workspace_bytes: max(1, chunks) * Kx *
+ *   Ky doubles; it needs no zeroing, no stale entry is ever read),
+ *   k_gram_final adds them in chunk order, one lane per entry.  Both are
+ *   launched on every call, also for m = 0.  smfv_gram_host is the rule in
+ *   plain C++.  smfv_gram_set_tiling (tests, A/B runs) forces one of the
+ *   register tilings of k_gram_partial: 0 = chosen by (Kx, Ky), 1 = 4 x 8,
+ *   2 = 2 x 4, 3 = 1 x 1 accumulators per lane; the bits are the same.
+ *
+ * smfv_block_mul_f64: Y = Z +- X C.  X is m x Kx, C is Kx x Ky on the device
+ *   with ldc >= Ky, Z and Y are m x Ky, Kx and Ky each in 1..128.  For every
+ *   (i, j): acc = Z[i,j], or +0.0 when d_Z == NULL; for l = 0 .. Kx-1
+ *   ascending: acc = fl(acc + fl(X[i,l] * c[l,j])); Y[i,j] = acc, where c = C,
+ *   or -C under SMFV_BLOCK_NEGATE (the flip is exact).  Bit-identical to that
+ *   loop, NaN and the sign of zero included.  Two aliases are legal: Y == Z
+ *   (same pointer and ld), and Y == X when Kx == Ky (same pointer and ld): the
+ *   kernel holds a row's X values in LDS, their loads waited for, before the
+ *   row's first store.  m = 0 launches nothing; otherwise one launch,
+ *   k_block_mul.
+ *
+ * smfv_small_solve_f64: C = G^-1 H.  G is K x K (K in 1..128, not modified),
+ *   H and C are K x N (N in 1..128), all on the device with leading
+ *   dimensions; C may be H (same pointer and ld).  LU without pivoting in the
+ *   order of the ILU(0) section, then its two solves:
+ *     factor, on a copy W of G: for i ascending and k < i ascending:
+ *       W[i,k] = fl(W[i,k] / W[k,k]); for j > k:
+ *       W[i,j] = fl(W[i,j] - fl(W[i,k] * W[k,j]));
+ *     forward: s = H[i,n]; for k < i ascending: s = fl(s - fl(W[i,k] * T[k,n]));
+ *       T[i,n] = s;
+ *     backward, i descending: s = T[i,n]; for k > i ascending:
+ *       s = fl(s - fl(W[i,k] * C[k,n])); C[i,n] = fl(s / W[i,i]).
+ *   Divisions are true IEEE divisions; a zero or non-finite pivot gives what
+ *   IEEE gives, there is no check and no read-back.  One launch of one block,
+ *   k_small_solve: W in LDS, right-looking elimination with a barrier per
+ *   pivot (every W[i,j] is updated once per k in ascending k, so the bits are
+ *   those of the row loop), one lane per right-hand-side column for the two
+ *   substitutions.  smfv_small_solve_host is the rule in plain C++.
+ *
+ * Refused with SMFV_ERR_INVALID before any device call: Kx, Ky, K or N outside
+ * 1..128, m < 0, a leading dimension below its width, unknown flag bits, a
+ * NULL output or workspace, a NULL block with m > 0 (a NULL G, H or C matrix
+ * always); in block_mul, Y sharing an element with Z or X other than by the
+ * two aliases above, and C sharing an element with Y; in small_solve, C
+ * sharing an element with G, or with H other than by C == H.
+ *
+ * Streams: every call is asynchronous on `stream` and graph-capturable -- no
+ * allocation, no synchronisation, no host read.
+ *
+ * A coupled block PCG built from these (CoupledBlockPCG in the Python package)
+ * has no breakdown guard: a rank-deficient block (a zero or repeated
+ * right-hand-side column, columns that become dependent) makes a Gram matrix
+ * singular and the IEEE infinities and NaNs propagate.
+ *
+ * Out of scope: a fused "X += P a, R -= Q a, rr" pass, dots fused into the
+ * SpMM stores, MFMA, deflation and the QR-stabilised block CG variants, other
+ * Krylov methods, distributed plans, the C++ drop-in, the CLI, bench.py. */
+#define SMFV_BLOCK_NEGATE 1 /* c = -C (exact) */
+#define SMFV_BLOCK_MAX_K 128
+SMFV_API int smfv_gram_workspace_bytes(int m, int Kx, int Ky, size_t *bytes);
+SMFV_API int smfv_gram_host(int m, int Kx, int Ky, const double *h_X, int64_t ldx, const double *h_Y, int64_t ldy,
+                            double *h_G, int64_t ldg);
+SMFV_API int smfv_gram_f64(int m, int Kx, int Ky, const double *d_X, int64_t ldx, const double *d_Y, int64_t ldy,
+                           double *d_G, int64_t ldg, double *d_workspace, void *stream);
+SMFV_API int smfv_gram_set_tiling(int tiling);
+SMFV_API int smfv_block_mul_f64(int m, int Kx, int Ky, int flags, const double *d_X, int64_t ldx, const double *d_C,
+                                int64_t ldc, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, void *stream);
+SMFV_API int smfv_small_solve_host(int K, int N, const double *h_G, int64_t ldg, const double *h_H, int64_t ldh,
+                                   double *h_C, int64_t ldc);
+SMFV_API int smfv_small_solve_f64(int K, int N, const double *d_G, int64_t ldg, const double *d_H, int64_t ldh,
+                                  double *d_C, int64_t ldc, void *stream);
 
 /* HBM streaming probe for the bench (not the SpMM path): d_dst = d_src,
  * `bytes` (multiple of 16, 16-B aligned pointers) by a 16-byte-per-lane

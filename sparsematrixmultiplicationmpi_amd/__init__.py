@@ -7,6 +7,7 @@ AlexisBalayre/SparseMatrixMultiplicationMPI).
     L U ~ A_csr on A's pattern           (ILU(0), ilu0 / Ilu0Preconditioner)
     B = P A P^T, few levels              (multicolour reordering, DeviceCSR.reordered)
     d[j] = X[:, j] . Y[:, j], Y += s X   (fixed-order column dots, scaled updates, BlockPCG)
+    G = X^T Y, Y = Z +- X C, C = G^-1 H  (Gram matrices, block updates, small solves, CoupledBlockPCG)
 
 The product is libsmfv.so (HIP kernels for gfx950 + C ABI in include/smfv.h)
 and libsmfv_mpi.so / smfv_main (the reference's C++ call surface and CLI).
@@ -31,7 +32,9 @@ from .inputs import (  # noqa: F401
     writeMatrixMarketFile,
 )
 from .engine import (  # noqa: F401
+    BLOCK_NEGATE,
     BlockPCG,
+    CoupledBlockPCG,
     DeviceCSR,
     Ilu0Plan,
     Ilu0Preconditioner,
@@ -40,6 +43,7 @@ from .engine import (  # noqa: F401
     TrsmPlan,
     VendorSpmm,
     Variant,
+    block_mul,
     col_axpy,
     col_xpay,
     coldot,
@@ -48,7 +52,10 @@ from .engine import (  # noqa: F401
     ilu0,
     ilu0_analyse,
     fill_x_hash,
+    gram,
+    gram_workspace_doubles,
     pcg_update,
+    small_solve,
     sparseMatrixFatVectorMultiply,
     sparseMatrixFatVectorMultiplyColumnWise,
     sparseMatrixFatVectorMultiplyNonZeroElement,

@@ -811,4 +811,38 @@ SMFV_API int smfv_coldot_host(int m, int K, const double *h_X, int64_t ldx, cons
     return SMFV_OK;
 }
 
+// Coupled blocks: the host half (the rules and the checks are in smfv_plan.cpp)
+SMFV_API int smfv_gram_workspace_bytes(int m, int Kx, int Ky, size_t *bytes)
+{
+    SMFV_REQUIRE(bytes, "gram_workspace_bytes: null argument");
+    SMFV_REQUIRE(Kx >= 1 && Kx <= smfv::BLOCK_MAX_K && Ky >= 1 && Ky <= smfv::BLOCK_MAX_K && m >= 0,
+                 "gram_workspace_bytes: m = %d, Kx = %d, Ky = %d", m, Kx, Ky);
+    *bytes = (size_t)smfv::coldot_chunks(m) * (size_t)Kx * (size_t)Ky * sizeof(double);
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_gram_host(int m, int Kx, int Ky, const double *h_X, int64_t ldx, const double *h_Y, int64_t ldy,
+                            double *h_G, int64_t ldg)
+{
+    std::string err;
+    if (!smfv::blockcg_check_gram(m, Kx, Ky, h_X, ldx, h_Y, ldy, h_G, ldg, h_G, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    smfv::gram_host(m, Kx, Ky, h_X, ldx, h_Y, ldy, h_G, ldg);
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_small_solve_host(int K, int N, const double *h_G, int64_t ldg, const double *h_H, int64_t ldh,
+                                   double *h_C, int64_t ldc)
+{
+    std::string err;
+    if (!smfv::blockcg_check_small_solve(K, N, h_G, ldg, h_H, ldh, h_C, ldc, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    smfv::small_solve_host(K, N, h_G, ldg, h_H, ldh, h_C, ldc);
+    return SMFV_OK;
+}
+
 }  // extern "C"

@@ -34,6 +34,11 @@
 //            per-column dots in a fixed order and per-column scaled updates of
 //            m x K blocks (smfv_coldot_f64, smfv_col_*_f64,
 //            smfv_pcg_update_f64); no counterpart in the reference
+//   k_gram_partial, k_gram_final, k_block_mul, k_small_solve
+//            Gram matrices X^T Y in the order of the column-dot rule, block
+//            times small matrix, a small dense solve (smfv_gram_f64,
+//            smfv_block_mul_f64, smfv_small_solve_f64); no counterpart in the
+//            reference
 //
 // Layout: X[n x K] and Y[m x K] row-major (SC/utils.cpp:216-228 serialize),
 // CSR int32/f64 as SC/MatrixDefinitions.h:14-19.
@@ -53,6 +58,7 @@
 // matrix touches stay in one XCD's L2.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdarg>
 #include <cstdlib>
@@ -5024,6 +5030,377 @@ SMFV_API int smfv_pcg_update_f64(int m, int K, const double *d_num, const double
 #undef LU
     SMFV_LAUNCHED();
     return coldot_final_launch(nchunks, K, d_workspace, d_rr, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Coupled blocks (smfv_gram_f64, smfv_block_mul_f64, smfv_small_solve_f64,
+// include/smfv.h): the K x K Gram matrix of two blocks in the order of the
+// column-dot rule, a block times a small matrix, a small dense solve.
+//
+// k_gram_partial.  A block of 256 lanes owns one chunk of 512 rows and one
+// tile of G; blockIdx.y walks the tiles.  A wavefront holds all 32 strands of
+// the chunk, two lanes per strand: lane l owns strand l / 2, the two lanes
+// split the tile's rows (GR_LI = 2) and the block's four wavefronts split its
+// columns (GR_LJ = 4).  A lane keeps a TI x TJ sub-tile of accumulators in
+// registers: per row of its strand it loads TI values of X and TJ of Y (16
+// bytes wide where the host found the alignment) and does TI * TJ separate
+// multiplies and adds, so a value is loaded once per sub-tile, not once per
+// entry of G; the next row's values are loaded before this row's arithmetic.
+// A strand's 16 rows are added in ascending order, then the tree
+// v[s] += v[s + h], h = 16 .. 1, is five __shfl_down by 2 h per accumulator --
+// every strand of the chunk sits in the lane's own wavefront, so there is no
+// LDS and no barrier.  Lanes 0 and 1 of a wavefront store the partials.  The
+// tile of G is (2 TI) x (4 TJ); a column past Kx / Ky is never loaded or
+// stored.  The additions per entry are those of k_coldot_partial whatever the
+// tiling.  k_gram_final: one lane per entry adds the partials in chunk order,
+// 32 loads ahead of the adds.
+//
+// k_block_mul.  pick_team's mapping: a team of TEAM lanes covers the Ky
+// columns of a row, VEC doubles per lane, 256 / TEAM row slots, R = 4 rows in
+// flight per slot.  c = +-C goes into LDS once per block (a lane reading
+// c[l][its columns] is conflict-free, the slots of a wavefront read the same
+// address), and a block walks row batches with a grid stride so that the copy
+// is shared by many rows.  Per batch every team stages the Kx values of its R
+// rows of X into LDS (row stride Kx | 1 doubles: the slots of a wavefront fall
+// on different banks); the barrier that follows is what makes Y == X legal --
+// every X value of the batch's rows is in LDS, its load waited for, before the
+// batch's first store, and no other block touches those rows.  Then
+// acc = Z, acc += x[l] * c[l] for l ascending, one store.
+//
+// k_small_solve.  One block.  W = G in LDS (row stride K | 1), right-looking
+// elimination: per pivot k a barrier, the column's quotients, a barrier, the
+// update of the trailing block.  Every W[i,j] receives its updates once per k
+// in ascending k from a row k that is final, which is the row loop's sequence
+// of operations.  Then lane n runs both substitutions for column n of H; the
+// forward result T lives in LDS when W and T fit the CU's 160 KiB together,
+// else in C itself (a lane reads and writes its own column only).
+// ---------------------------------------------------------------------------
+namespace smfv {
+
+constexpr int GR_LI = 2, GR_LJ = 4;  // lanes of a strand over a tile's rows, wavefronts over its columns
+
+// v[0..N) = p[0..N), V doubles per load; a column at or past K, or a missing row, is +0.0
+template <int N, int V> __device__ __forceinline__ void gram_load(double (&v)[N], const double *p, int c0, int K, bool row_ok)
+{
+#pragma unroll
+    for (int a = 0; a < N; a += V) {
+        if (row_ok && c0 + a < K) {  // V == 2: K and c0 + a are even, the pair is inside
+            if constexpr (V == 2) {
+                const bv_d2 t = bv_load(reinterpret_cast<const bv_d2 *>(p + a));
+                v[a] = t.x;
+                v[a + 1] = t.y;
+            } else {
+                v[a] = bv_load(p + a);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < V; ++u) v[a + u] = 0.0;
+        }
+    }
+}
+
+// nchunks = max(1, chunks of m) blocks in x: for m = 0 chunk 0 is written as +0.0
+template <int TI, int TJ, int VEC>
+__global__ __launch_bounds__(256) void k_gram_partial(int m, int Kx, int Ky, int tiles_j, const double *X, int64_t ldx,
+                                                      const double *Y, int64_t ldy, double *__restrict__ ws)
+{
+    constexpr int VX = (VEC == 2 && TI % 2 == 0) ? 2 : 1, VY = (VEC == 2 && TJ % 2 == 0) ? 2 : 1;
+    static_assert(BV_T % 2 == 0 && BV_STRANDS * GR_LI == 64, "a wavefront holds every strand of a chunk");
+    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+    const int s = lane / GR_LI, li = lane % GR_LI;
+    const int ti = (int)blockIdx.y / tiles_j, tj = (int)blockIdx.y - ti * tiles_j;
+    const int i0 = (ti * GR_LI + li) * TI, j0 = (tj * GR_LJ + wv) * TJ;
+    const int64_t row0 = (int64_t)blockIdx.x * BV_CHUNK + s;
+    const bool full = ((int64_t)blockIdx.x + 1) * BV_CHUNK <= m;  // every row of the chunk exists
+    double acc[TI][TJ];
+#pragma unroll
+    for (int a = 0; a < TI; ++a)
+#pragma unroll
+        for (int b = 0; b < TJ; ++b) acc[a][b] = 0.0;
+    // the next step's values are loaded before this step's multiplies and adds
+    double x[2][TI], y[2][TJ];
+    {
+        const bool ok = full || row0 < m;
+        gram_load<TI, VX>(x[0], X + row0 * ldx + i0, i0, Kx, ok);
+        gram_load<TJ, VY>(y[0], Y + row0 * ldy + j0, j0, Ky, ok);
+    }
+#pragma unroll 1
+    for (int t0 = 0; t0 < BV_T; t0 += 2) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int64_t row = row0 + (int64_t)(t0 + u + 1) * BV_STRANDS;  // past the chunk after its last step: not loaded
+            const bool ok = t0 + u + 1 < BV_T && (full || row < m);
+            gram_load<TI, VX>(x[1 - u], X + row * ldx + i0, i0, Kx, ok);
+            gram_load<TJ, VY>(y[1 - u], Y + row * ldy + j0, j0, Ky, ok);
+#pragma unroll
+            for (int a = 0; a < TI; ++a)
+#pragma unroll
+                for (int b = 0; b < TJ; ++b) acc[a][b] = acc[a][b] + x[u][a] * y[u][b];  // a missing row adds +0.0
+        }
+    }
+#pragma unroll
+    for (int h = BV_STRANDS / 2; h >= 1; h >>= 1)
+#pragma unroll
+        for (int a = 0; a < TI; ++a)
+#pragma unroll
+            for (int b = 0; b < TJ; ++b) acc[a][b] = acc[a][b] + __shfl_down(acc[a][b], h * GR_LI, 64);
+    if (s == 0) {
+        double *out = ws + (int64_t)blockIdx.x * Kx * Ky;
+#pragma unroll
+        for (int a = 0; a < TI; ++a)
+#pragma unroll
+            for (int b = 0; b < TJ; ++b)
+                if (i0 + a < Kx && j0 + b < Ky) out[(i0 + a) * Ky + j0 + b] = acc[a][b];
+    }
+}
+
+// G[i,j] = ((+0.0 + ws[0][i,j]) + ws[1][i,j]) + ...: one lane per entry
+__global__ __launch_bounds__(256) void k_gram_final(int nchunks, int Kx, int Ky, const double *__restrict__ ws,
+                                                    double *__restrict__ G, int64_t ldg)
+{
+    constexpr int B = 32;
+    const int n = Kx * Ky, e = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (e >= n) return;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < nchunks; c0 += B) {
+        double v[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) v[u] = c0 + u < nchunks ? ws[(int64_t)(c0 + u) * n + e] : 0.0;
+#pragma unroll
+        for (int u = 0; u < B; ++u) acc = acc + v[u];  // + (+0.0) past the end changes nothing
+    }
+    const int i = e / Ky;
+    G[i * ldg + (e - i * Ky)] = acc;
+}
+
+constexpr int BM_R = 4;  // rows in flight per row slot of k_block_mul
+
+// Y = Z + X c, c = +-C.  X, Z and Y carry no __restrict__: Y may be Z or X.
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(256) void k_block_mul(int m, int Kx, int Ky, int flags, int64_t nbatches, const double *X,
+                                                   int64_t ldx, const double *__restrict__ C, int64_t ldc,
+                                                   const double *Z, int64_t ldz, double *Y, int64_t ldy)
+{
+    using T = typename BvT<VEC>::T;
+    constexpr int RPB = 256 / TEAM, R = BM_R;
+    extern __shared__ __attribute__((aligned(16))) double bm_lds[];
+    double *cs = bm_lds;                          // Kx x Ky, packed
+    double *xs = bm_lds + ((Kx * Ky + 1) & ~1);   // RPB * R rows of X, stride xld
+    const int xld = Kx | 1;
+    const int tid = (int)threadIdx.x, tl = tid & (TEAM - 1), q = tid / TEAM;
+    for (int e = tid; e < Kx * Ky; e += 256) {
+        const int l = e / Ky;
+        const double v = C[l * ldc + (e - l * Ky)];
+        cs[e] = (flags & SMFV_BLOCK_NEGATE) ? -v : v;
+    }
+    const int nv = Ky / VEC;  // VEC == 2 only for an even Ky
+    for (int64_t b = blockIdx.x; b < nbatches; b += gridDim.x) {  // block-uniform
+        const int64_t r0 = b * (RPB * R) + q;
+        __syncthreads();  // c is written; the batch before has been read
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int64_t row = r0 + u * RPB;
+            if (row < m)
+                for (int l = tl; l < Kx; l += TEAM) xs[(u * RPB + q) * xld + l] = bv_load(X + row * ldx + l);
+        }
+        __syncthreads();  // every X value of the batch's rows is in LDS before the batch's first store
+        for (int c0 = 0; c0 < nv; c0 += TEAM) {
+            const int c = c0 + tl;
+            if (c >= nv) continue;
+            T acc[R];
+            bool ok[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const int64_t row = r0 + u * RPB;
+                ok[u] = row < m;
+                acc[u] = bv_zero(T{});
+                if (ok[u] && Z) acc[u] = *(reinterpret_cast<const T *>(Z + row * ldz) + c);
+            }
+            const T *cp = reinterpret_cast<const T *>(cs) + c;
+            const double *xp = xs + q * xld;
+#pragma unroll 4
+            for (int l = 0; l < Kx; ++l) {
+                const T cv = cp[l * nv];
+#pragma unroll
+                for (int u = 0; u < R; ++u) acc[u] = acc[u] + cv * xp[u * RPB * xld + l];
+            }
+#pragma unroll
+            for (int u = 0; u < R; ++u)
+                if (ok[u]) *(reinterpret_cast<T *>(Y + (r0 + u * RPB) * ldy) + c) = acc[u];
+        }
+    }
+}
+
+// the two substitutions of column n = threadIdx.x; TL: T is in LDS, else T is C
+template <bool TL>
+__device__ __forceinline__ void small_subst(int K, int N, const double *W, int ldw, const double *H, int64_t ldh, double *C,
+                                            int64_t ldc, double *T, int64_t ldt)
+{
+    const int n = (int)threadIdx.x;
+    if (n >= N) return;
+    for (int i = 0; i < K; ++i) {
+        double s = H[i * ldh + n];
+#pragma unroll 8  // the reads of eight steps ahead of their dependent subtractions
+        for (int k = 0; k < i; ++k) s = s - W[i * ldw + k] * T[k * ldt + n];
+        T[i * ldt + n] = s;
+    }
+    for (int i = K - 1; i >= 0; --i) {
+        double s = T[i * ldt + n];
+#pragma unroll 8
+        for (int k = i + 1; k < K; ++k) s = s - W[i * ldw + k] * T[k * ldt + n];
+        s = s / W[i * ldw + i];
+        T[i * ldt + n] = s;
+        if (TL) C[i * ldc + n] = s;
+    }
+}
+
+// tw: lanes across a row of the trailing block (a power of two <= blockDim.x)
+__global__ __launch_bounds__(1024) void k_small_solve(int K, int N, int tw, int t_lds, const double *G, int64_t ldg,
+                                                      const double *H, int64_t ldh, double *C, int64_t ldc)
+{
+    extern __shared__ __attribute__((aligned(16))) double ss_lds[];
+    const int ldw = K | 1;
+    double *W = ss_lds;
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    for (int e = tid; e < K * K; e += nt) {
+        const int i = e / K;
+        W[i * ldw + (e - i * K)] = G[i * ldg + (e - i * K)];
+    }
+    const int tx = tid & (tw - 1), ty = tid / tw, nty = nt / tw;
+    for (int k = 0; k + 1 < K; ++k) {  // block-uniform
+        __syncthreads();  // row k and column k carry every update of the pivots before k
+        const double p = W[k * ldw + k];
+        for (int i = k + 1 + tid; i < K; i += nt) W[i * ldw + k] = W[i * ldw + k] / p;
+        __syncthreads();
+        for (int i = k + 1 + ty; i < K; i += nty) {
+            const double l = W[i * ldw + k];
+            for (int j = k + 1 + tx; j < K; j += tw) W[i * ldw + j] = W[i * ldw + j] - l * W[k * ldw + j];
+        }
+    }
+    __syncthreads();
+    if (t_lds) small_subst<true>(K, N, W, ldw, H, ldh, C, ldc, W + K * ldw, N);
+    else small_subst<false>(K, N, W, ldw, H, ldh, C, ldc, C, ldc);
+}
+
+}  // namespace smfv
+
+namespace {
+
+std::atomic<int> g_gram_tiling{0};  // smfv_gram_set_tiling
+constexpr int BM_CUS = 256;         // an MI355X's compute units: the grid of k_block_mul is a few blocks for each
+constexpr size_t LDS_CU = 160 * 1024, LDS_DEFAULT = 64 * 1024;
+
+// a launch with more dynamic LDS than the default limit has to raise the kernel's own first
+int raise_lds_limit(const void *kernel, size_t bytes)
+{
+    if (bytes > LDS_DEFAULT) SMFV_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SMFV_OK;
+}
+
+template <int TEAM, int VEC>
+int block_mul_launch(unsigned nblk, size_t lds, hipStream_t st, int m, int Kx, int Ky, int flags, int64_t nbatches,
+                     const double *X, int64_t ldx, const double *C, int64_t ldc, const double *Z, int64_t ldz, double *Y,
+                     int64_t ldy)
+{
+    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&k_block_mul<TEAM, VEC>), lds);
+    if (rc != SMFV_OK) return rc;
+    hipLaunchKernelGGL((k_block_mul<TEAM, VEC>), dim3(nblk), dim3(256), lds, st, m, Kx, Ky, flags, nbatches, X, ldx, C, ldc, Z,
+                       ldz, Y, ldy);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+SMFV_API int smfv_gram_set_tiling(int tiling)
+{
+    SMFV_REQUIRE(tiling >= 0 && tiling <= 3, "gram_set_tiling: %d, must be 0 (by size), 1 (4 x 8), 2 (2 x 4) or 3 (1 x 1)", tiling);
+    g_gram_tiling.store(tiling);
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_gram_f64(int m, int Kx, int Ky, const double *d_X, int64_t ldx, const double *d_Y, int64_t ldy, double *d_G,
+                           int64_t ldg, double *d_workspace, void *stream)
+{
+    std::string err;
+    if (!blockcg_check_gram(m, Kx, Ky, d_X, ldx, d_Y, ldy, d_G, ldg, d_workspace, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    hipStream_t st = as_stream(stream);
+    const int nchunks = (int)coldot_chunks(m);
+    int tiling = g_gram_tiling.load();
+    if (tiling == 0) tiling = (Kx <= 2 && Ky <= 4) ? 3 : (Kx <= 4 && Ky <= 16) ? 2 : 1;
+    const int ti = tiling == 1 ? 4 : tiling == 2 ? 2 : 1, tj = tiling == 1 ? 8 : tiling == 2 ? 4 : 1;
+    const int tiles_i = (Kx + GR_LI * ti - 1) / (GR_LI * ti), tiles_j = (Ky + GR_LJ * tj - 1) / (GR_LJ * tj);
+    // 16-byte loads need both blocks aligned, even widths and even leading dimensions
+    const int vec = (Kx % 2 == 0 && Ky % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && aligned16(d_X) && aligned16(d_Y)) ? 2 : 1;
+    const dim3 grid((unsigned)nchunks, (unsigned)(tiles_i * tiles_j));
+#define LG(TI_, TJ_, V_) hipLaunchKernelGGL((k_gram_partial<TI_, TJ_, V_>), grid, dim3(256), 0, st, m, Kx, Ky, tiles_j, d_X, ldx, d_Y, ldy, d_workspace)
+    switch (tiling * 4 + vec) {
+    case 1 * 4 + 1: LG(4, 8, 1); break;
+    case 1 * 4 + 2: LG(4, 8, 2); break;
+    case 2 * 4 + 1: LG(2, 4, 1); break;
+    case 2 * 4 + 2: LG(2, 4, 2); break;
+    default: LG(1, 1, 1); break;
+    }
+#undef LG
+    SMFV_LAUNCHED();
+    hipLaunchKernelGGL(k_gram_final, dim3((unsigned)((Kx * Ky + 255) / 256)), dim3(256), 0, st, nchunks, Kx, Ky, d_workspace, d_G,
+                       ldg);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_block_mul_f64(int m, int Kx, int Ky, int flags, const double *d_X, int64_t ldx, const double *d_C,
+                                int64_t ldc, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, void *stream)
+{
+    std::string err;
+    if (!blockcg_check_block_mul(m, Kx, Ky, flags, d_X, ldx, d_C, ldc, d_Z, ldz, d_Y, ldy, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    if (m == 0) return SMFV_OK;
+    const int vec = d_Z ? pick_vec(d_Z, ldz, d_Y, ldy, Ky) : pick_vec(d_Y, ldy, d_Y, ldy, Ky);
+    int team = pick_team(Ky, vec);
+    const size_t xld = (size_t)(Kx | 1);
+    // the staged rows of X stay within 32 KiB: a wide X takes a wider team (fewer row slots)
+    while (team < 64 && (size_t)(256 / team) * BM_R * xld * 8 > 32 * 1024) team <<= 1;
+    const int rows = 256 / team * BM_R;
+    const int64_t nbatches = ((int64_t)m + rows - 1) / rows;
+    const size_t lds = ((size_t)((Kx * Ky + 1) & ~1) + (size_t)rows * xld) * sizeof(double);
+    const int64_t resident = (int64_t)BM_CUS * std::min<size_t>(8, LDS_CU / lds);
+    const unsigned nblk = (unsigned)std::min<int64_t>(nbatches, resident);
+    hipStream_t st = as_stream(stream);
+#define LM(T_, V_) { const int rc_ = block_mul_launch<T_, V_>(nblk, lds, st, m, Kx, Ky, flags, nbatches, d_X, ldx, d_C, ldc, d_Z, ldz, d_Y, ldy); if (rc_ != SMFV_OK) return rc_; }
+    SMFV_TEAM_SWITCH(team, vec, LM)
+#undef LM
+    return SMFV_OK;
+}
+
+SMFV_API int smfv_small_solve_f64(int K, int N, const double *d_G, int64_t ldg, const double *d_H, int64_t ldh, double *d_C,
+                                  int64_t ldc, void *stream)
+{
+    std::string err;
+    if (!blockcg_check_small_solve(K, N, d_G, ldg, d_H, ldh, d_C, ldc, &err)) {
+        set_error("%s", err.c_str());
+        return SMFV_ERR_INVALID;
+    }
+    const size_t w_bytes = (size_t)K * (size_t)(K | 1) * sizeof(double), t_bytes = (size_t)K * (size_t)N * sizeof(double);
+    const int t_lds = w_bytes + t_bytes <= LDS_CU ? 1 : 0;
+    const size_t lds = w_bytes + (t_lds ? t_bytes : 0);
+    int tw = 1;
+    while (tw < K && tw < 64) tw <<= 1;
+    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&k_small_solve), lds);
+    if (rc != SMFV_OK) return rc;
+    hipLaunchKernelGGL(k_small_solve, dim3(1), dim3(K <= 32 ? 256 : 1024), lds, as_stream(stream), K, N, tw, t_lds, d_G, ldg, d_H,
+                       ldh, d_C, ldc);
+    SMFV_LAUNCHED();
+    return SMFV_OK;
 }
 
 }  // extern "C"

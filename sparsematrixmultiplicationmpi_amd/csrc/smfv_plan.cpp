@@ -2358,4 +2358,131 @@ bool blockvec_check_pcg_update(int m, int K, const void *num, int flags, const v
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Coupled blocks: the Gram and small-solve rules on the host and the argument
+// checks (smfv_plan.h).
+// ---------------------------------------------------------------------------
+void gram_host(int m, int Kx, int Ky, const double *X, int64_t ldx, const double *Y, int64_t ldy, double *G, int64_t ldg)
+{
+    for (int i = 0; i < Kx; ++i)
+        for (int j = 0; j < Ky; ++j) {
+            double d = 0.0;
+            for (int64_t c0 = 0; c0 < m; c0 += COLDOT_CHUNK) {
+                const int64_t end = std::min<int64_t>(m, c0 + COLDOT_CHUNK);
+                double v[COLDOT_STRANDS];
+                for (int s = 0; s < COLDOT_STRANDS; ++s) {
+                    double a = 0.0;
+                    for (int64_t r = c0 + s; r < end; r += COLDOT_STRANDS) a = a + X[r * ldx + i] * Y[r * ldy + j];
+                    v[s] = a;
+                }
+                for (int h = COLDOT_STRANDS / 2; h >= 1; h /= 2)
+                    for (int s = 0; s < h; ++s) v[s] = v[s] + v[s + h];
+                d = d + v[0];
+            }
+            G[i * ldg + j] = d;
+        }
+}
+
+void small_solve_host(int K, int N, const double *G, int64_t ldg, const double *H, int64_t ldh, double *C, int64_t ldc)
+{
+    std::vector<double> W((size_t)K * K), T((size_t)K * N);
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < K; ++j) W[(size_t)i * K + j] = G[i * ldg + j];
+    for (int i = 0; i < K; ++i)
+        for (int k = 0; k < i; ++k) {
+            const double l = W[(size_t)i * K + k] / W[(size_t)k * K + k];
+            W[(size_t)i * K + k] = l;
+            for (int j = k + 1; j < K; ++j) W[(size_t)i * K + j] = W[(size_t)i * K + j] - l * W[(size_t)k * K + j];
+        }
+    for (int n = 0; n < N; ++n) {
+        for (int i = 0; i < K; ++i) {
+            double s = H[i * ldh + n];
+            for (int k = 0; k < i; ++k) s = s - W[(size_t)i * K + k] * T[(size_t)k * N + n];
+            T[(size_t)i * N + n] = s;
+        }
+        for (int i = K - 1; i >= 0; --i) {
+            double s = T[(size_t)i * N + n];
+            for (int k = i + 1; k < K; ++k) s = s - W[(size_t)i * K + k] * T[(size_t)k * N + n];
+            T[(size_t)i * N + n] = s / W[(size_t)i * K + i];
+        }
+    }
+    for (int i = 0; i < K; ++i)  // H is read whole before C is written: C may be H
+        for (int n = 0; n < N; ++n) C[i * ldc + n] = T[(size_t)i * N + n];
+}
+
+namespace {
+
+bool blockcg_width(const char *name, const char *which, int K, std::string *err)
+{
+    if (K < 1 || K > BLOCK_MAX_K)
+        return blockvec_fail(err, name, (std::string(which) + " = " + std::to_string(K) + ", must be in 1.." + std::to_string(BLOCK_MAX_K)).c_str());
+    return true;
+}
+
+bool blockcg_matrix(const char *name, const char *which, int cols, const void *p, int64_t ld, std::string *err)
+{
+    if (ld < cols) return blockvec_fail(err, name, (std::string("leading dimension of ") + which + " smaller than its width").c_str());
+    if (!p) return blockvec_fail(err, name, (std::string("null ") + which).c_str());
+    return true;
+}
+
+// do the ra x ca window (a, lda) and the rb x cb window (b, ldb) share an element?
+bool windows_meet(int64_t ra, int ca, const void *a, int64_t lda, int64_t rb, int cb, const void *b, int64_t ldb)
+{
+    if (ra == 0 || rb == 0 || !a || !b) return false;
+    int64_t pa = (int64_t)(reinterpret_cast<uintptr_t>(a)), pb = (int64_t)(reinterpret_cast<uintptr_t>(b));
+    const int64_t ea = pa + 8 * ((ra - 1) * lda + ca), eb = pb + 8 * ((rb - 1) * ldb + cb);
+    if (ea <= pb || eb <= pa) return false;  // the byte ranges do not meet
+    const int64_t d = pa > pb ? pa - pb : pb - pa;
+    if (lda != ldb || d % 8 != 0) return true;  // interleaved in no simple way: refused
+    const int64_t r = (d / 8) % lda;            // column shift of the higher window against the lower
+    const int clo = pa <= pb ? ca : cb, chi = pa <= pb ? cb : ca;
+    return r < clo || r + chi > lda;
+}
+
+}  // namespace
+
+bool blockcg_check_gram(int m, int Kx, int Ky, const void *X, int64_t ldx, const void *Y, int64_t ldy, const void *G,
+                        int64_t ldg, const void *ws, std::string *err)
+{
+    const char *name = "gram";
+    if (!blockcg_width(name, "Kx", Kx, err) || !blockcg_width(name, "Ky", Ky, err)) return false;
+    if (m < 0) return blockvec_fail(err, name, ("m = " + std::to_string(m) + ", must not be negative").c_str());
+    if (!blockvec_block(name, "X", m, Kx, X, ldx, err) || !blockvec_block(name, "Y", m, Ky, Y, ldy, err)) return false;
+    if (ldg < Ky) return blockvec_fail(err, name, "leading dimension of G smaller than Ky");
+    if (!G) return blockvec_fail(err, name, "null G");
+    if (!ws) return blockvec_fail(err, name, "null workspace");
+    return true;
+}
+
+bool blockcg_check_block_mul(int m, int Kx, int Ky, int flags, const void *X, int64_t ldx, const void *C, int64_t ldc,
+                             const void *Z, int64_t ldz, const void *Y, int64_t ldy, std::string *err)
+{
+    const char *name = "block_mul";
+    if (!blockcg_width(name, "Kx", Kx, err) || !blockcg_width(name, "Ky", Ky, err)) return false;
+    if (m < 0) return blockvec_fail(err, name, ("m = " + std::to_string(m) + ", must not be negative").c_str());
+    if (flags & ~BLOCK_FLAGS) return blockvec_fail(err, name, ("unknown flags " + std::to_string(flags)).c_str());
+    if (!blockvec_block(name, "X", m, Kx, X, ldx, err) || !blockvec_block(name, "Y", m, Ky, Y, ldy, err)) return false;
+    if (Z && ldz < Ky) return blockvec_fail(err, name, "leading dimension of Z smaller than K");
+    if (!blockcg_matrix(name, "C", Ky, C, ldc, err)) return false;
+    if (!(Z == Y && ldz == ldy) && windows_meet(m, Ky, Z, ldz, m, Ky, Y, ldy)) return blockvec_fail(err, name, "Z and Y overlap");
+    if (!(X == Y && ldx == ldy && Kx == Ky) && windows_meet(m, Kx, X, ldx, m, Ky, Y, ldy))
+        return blockvec_fail(err, name, "X and Y overlap");
+    if (windows_meet(Kx, Ky, C, ldc, m, Ky, Y, ldy)) return blockvec_fail(err, name, "C and Y overlap");
+    return true;
+}
+
+bool blockcg_check_small_solve(int K, int N, const void *G, int64_t ldg, const void *H, int64_t ldh, const void *C,
+                               int64_t ldc, std::string *err)
+{
+    const char *name = "small_solve";
+    if (!blockcg_width(name, "K", K, err) || !blockcg_width(name, "N", N, err)) return false;
+    if (!blockcg_matrix(name, "G", K, G, ldg, err) || !blockcg_matrix(name, "H", N, H, ldh, err) ||
+        !blockcg_matrix(name, "C", N, C, ldc, err))
+        return false;
+    if (windows_meet(K, K, G, ldg, K, N, C, ldc)) return blockvec_fail(err, name, "G and C overlap");
+    if (!(H == C && ldh == ldc) && windows_meet(K, N, H, ldh, K, N, C, ldc)) return blockvec_fail(err, name, "H and C overlap");
+    return true;
+}
+
 }  // namespace smfv

@@ -521,4 +521,28 @@ bool blockvec_check_pcg_update(int m, int K, const void *num, int flags, const v
                                int64_t ldq, const void *X, int64_t ldx, const void *R, int64_t ldr, const void *rr,
                                const void *ws, std::string *err);
 
+// ---------------------------------------------------------------------------
+// Coupled blocks (smfv_gram_*, smfv_block_mul_f64, smfv_small_solve_*,
+// include/smfv.h): the two rules a device kernel restates, in plain C++, and
+// the argument checks every device entry runs before its first device call.
+// Host only.
+// ---------------------------------------------------------------------------
+constexpr int BLOCK_MAX_K = 128;  // SMFV_BLOCK_MAX_K: the widest block and small system
+constexpr int BLOCK_FLAGS = 1;    // SMFV_BLOCK_NEGATE
+
+// G[i * ldg + j] = the column-dot rule on column i of X and column j of Y.
+void gram_host(int m, int Kx, int Ky, const double *X, int64_t ldx, const double *Y, int64_t ldy, double *G, int64_t ldg);
+// C = G^-1 H by the small-solve rule (LU without pivoting, forward, backward);
+// C may be H.
+void small_solve_host(int K, int N, const double *G, int64_t ldg, const double *H, int64_t ldh, double *C, int64_t ldc);
+
+bool blockcg_check_gram(int m, int Kx, int Ky, const void *X, int64_t ldx, const void *Y, int64_t ldy, const void *G,
+                        int64_t ldg, const void *ws, std::string *err);
+// Y == Z, and Y == X for Kx == Ky, are legal with the same pointer and ld;
+// every other shared element of Y with X, Z or C is refused.
+bool blockcg_check_block_mul(int m, int Kx, int Ky, int flags, const void *X, int64_t ldx, const void *C, int64_t ldc,
+                             const void *Z, int64_t ldz, const void *Y, int64_t ldy, std::string *err);
+bool blockcg_check_small_solve(int K, int N, const void *G, int64_t ldg, const void *H, int64_t ldh, const void *C,
+                               int64_t ldc, std::string *err);
+
 }  // namespace smfv

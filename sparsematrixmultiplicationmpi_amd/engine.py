@@ -955,6 +955,301 @@ class BlockPCG:
         return self.X, self.iterations, rel
 
 
+BLOCK_NEGATE = 1  # SMFV_BLOCK_NEGATE
+BLOCK_MAX_K = 128  # SMFV_BLOCK_MAX_K
+
+
+def gram_workspace_doubles(m: int, Kx: int, Ky: int) -> int:
+    b = c_size_t(0)
+    call("smfv_gram_workspace_bytes", int(m), int(Kx), int(Ky), byref(b))
+    return b.value // 8
+
+
+def gram_set_tiling(tiling: int = 0) -> None:
+    """Force a register tiling of k_gram_partial (tests, A/B runs): 0 = by
+    (Kx, Ky), 1 = 4 x 8, 2 = 2 x 4, 3 = 1 x 1.  The bits do not depend on it."""
+    call("smfv_gram_set_tiling", int(tiling))
+
+
+def _check_small(T: torch.Tensor, rows: int, cols: int, name: str, like: torch.Tensor) -> int:
+    """A small dense matrix on `like`'s device: (rows, cols), row-major; its leading dimension."""
+    if not T.is_cuda or T.dtype != torch.float64 or T.device != like.device:
+        raise TypeError(f"{name} must be a float64 HIP tensor on {like.device}")
+    if T.dim() != 2 or tuple(T.shape) != (rows, cols):
+        raise ValueError(f"{name} must have shape ({rows}, {cols}), got {tuple(T.shape)}")
+    if cols > 1 and T.stride(1) != 1:
+        raise ValueError(f"{name} must be row-major (unit column stride)")
+    return max(int(T.stride(0)), cols) if rows > 1 else cols
+
+
+def gram(X: torch.Tensor, Y: torch.Tensor, out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+         workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """out = X^T Y (Kx x Ky), every entry in the fixed order of the column-dot
+    rule: out[i, j] == coldot(X[:, i], Y[:, j]) bit for bit (smfv_gram_f64),
+    asynchronous on `stream`.  X may be Y; Kx and Ky are at most 128.  Without
+    `out` / `workspace` (gram_workspace_doubles entries) they are allocated
+    here; a caller that captures passes both."""
+    m, Kx = _block_shape(X, "X")
+    my, Ky = _block_shape(Y, "Y")
+    if my != m:
+        raise ValueError(f"X has {m} rows, Y has {my}")
+    ldx = _check_dense(X, m, Kx, "X")
+    ldy = _check_dense(Y, m, Ky, "Y")
+    _same_device(X, Y, "Y")
+    if out is None:
+        out = torch.empty((Kx, Ky), dtype=torch.float64, device=X.device)
+    ldg = _check_small(out, Kx, Ky, "out", X)
+    need = gram_workspace_doubles(m, Kx, Ky)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=X.device)
+    elif not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous() \
+            or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous float64 HIP tensor of {need} entries")
+    call("smfv_gram_f64", m, Kx, Ky, X.data_ptr(), ldx, Y.data_ptr(), ldy, out.data_ptr(), ldg, workspace.data_ptr(),
+         stream_handle(stream))
+    return out
+
+
+def block_mul(X: torch.Tensor, C: torch.Tensor, Z: torch.Tensor | None = None, Y: torch.Tensor | None = None,
+              negate: bool = False, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Y = Z + X C (Z None: Y = X C), or Y = Z - X C with negate; per entry
+    the products are added to Z[i, j] one by one for l ascending
+    (smfv_block_mul_f64).  X is m x Kx, C is Kx x Ky on the device, Z and Y
+    are m x Ky.  Y may be Z, and Y may be X when Kx == Ky; any other overlap
+    is refused.  Without Y a new block is returned."""
+    m, Kx = _block_shape(X, "X")
+    if C.dim() != 2 or C.shape[0] != Kx:
+        raise ValueError(f"C must have shape ({Kx}, Ky), got {tuple(C.shape)}")
+    Ky = int(C.shape[1])
+    ldx = _check_dense(X, m, Kx, "X")
+    ldc = _check_small(C, Kx, Ky, "C", X)
+    if Y is None:
+        Y = torch.empty((m, Ky), dtype=torch.float64, device=X.device)
+    ldy = _check_dense(Y, m, Ky, "Y")
+    _same_device(X, Y, "Y")
+    ldz = 0
+    if Z is not None:
+        ldz = _check_dense(Z, m, Ky, "Z")
+        _same_device(X, Z, "Z")
+    call("smfv_block_mul_f64", m, Kx, Ky, BLOCK_NEGATE if negate else 0, X.data_ptr(), ldx, C.data_ptr(), ldc,
+         Z.data_ptr() if Z is not None else 0, ldz, Y.data_ptr(), ldy, stream_handle(stream))
+    return Y
+
+
+def small_solve(G: torch.Tensor, H: torch.Tensor, out: torch.Tensor | None = None,
+                stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """out = G^-1 H for a K x K matrix G and a K x N matrix H on the device
+    (K, N <= 128): LU without pivoting and two substitutions in one launch
+    (smfv_small_solve_f64), no host read.  A zero pivot gives what IEEE gives.
+    `out` may be H."""
+    if G.dim() != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+        raise ValueError(f"G must be square, got {tuple(G.shape)}")
+    if not G.is_cuda or G.dtype != torch.float64:
+        raise TypeError("G must be a float64 HIP tensor")
+    K = int(G.shape[0])
+    if H.dim() != 2 or H.shape[0] != K or H.shape[1] < 1:
+        raise ValueError(f"H must have shape ({K}, N), got {tuple(H.shape)}")
+    N = int(H.shape[1])
+    ldg = _check_small(G, K, K, "G", G)
+    ldh = _check_small(H, K, N, "H", G)
+    if out is None:
+        out = torch.empty((K, N), dtype=torch.float64, device=G.device)
+    ldc = _check_small(out, K, N, "out", G)
+    call("smfv_small_solve_f64", K, N, G.data_ptr(), ldg, H.data_ptr(), ldh, out.data_ptr(), ldc, stream_handle(stream))
+    return out
+
+
+class CoupledBlockPCG:
+    """Block preconditioned conjugate gradients (O'Leary) on K right-hand
+    sides: A X = B for a symmetric positive definite A, the columns coupled
+    through K x K Gram matrices.  Every step searches the whole K-dimensional
+    block space, so it needs fewer iterations than BlockPCG, whose columns are
+    K conjugate-gradient runs of their own.
+
+    A, M, K and the methods are BlockPCG's: A a DeviceCSR (a ROWWISE SpmmPlan
+    is made) or a non-transposed SpmmPlan, M anything with
+    apply(X, Y, stream=...) or None; K is at most 128.  Every block (X, R, P,
+    Q, Z), the K x K matrices and the Gram workspace are allocated here, once.
+
+    start: R = B - A X0, Z = M(R), P = Z, rho = gram(Z, R), bb = coldot(B, B).
+    An iteration is Q = A P; Gamma = gram(P, Q); alpha = small_solve(Gamma,
+    rho); X += P alpha; R -= Q alpha; Z = M(R); rho' = gram(Z, R);
+    beta = small_solve(rho, rho'); P = Z + P beta; rho <- rho' by swapping
+    buffers.  rr is diag(rho') when M is None, else one coldot(R, R).
+    iterate() makes no host read, allocation or synchronisation and captures
+    into a graph; as in BlockPCG the rho buffers swap every iteration, so
+    capture an EVEN number of iterations (solve(graph=True) keeps one graph
+    per parity).
+
+    Limits.  There is no breakdown guard like BlockPCG's zero-denominator
+    flag: a rank-deficient block -- a zero or repeated right-hand-side column,
+    or columns that become dependent as they converge -- makes Gamma or rho
+    singular, and the IEEE infinities and NaNs propagate into every column.
+    solve() stops at the first check where any rr is non-finite, sets
+    self.breakdown = True and returns as usual.  Deflation and the
+    QR-stabilised variants are out of scope."""
+
+    def __init__(self, A, K: int, M=None, stream: torch.cuda.Stream | None = None):
+        if isinstance(A, SpmmPlan):
+            if A._transposed or A.rows is not None:
+                raise ValueError("CoupledBlockPCG needs a plan of the whole A, not a transposed or a row-block plan")
+            if A.K != int(K):
+                raise ValueError(f"the plan was made for K = {A.K}, not {K}")
+            self.plan, self.A = A, A.A
+        elif isinstance(A, DeviceCSR):
+            if not 1 <= int(K) <= BLOCK_MAX_K:
+                raise ValueError(f"K = {K}, must be in 1..{BLOCK_MAX_K}")
+            self.plan, self.A = SpmmPlan(Variant.ROWWISE, A, int(K), stream=stream), A
+        else:
+            raise TypeError("A must be a DeviceCSR or an SpmmPlan")
+        if not 1 <= int(K) <= BLOCK_MAX_K:
+            raise ValueError(f"K = {K}, must be in 1..{BLOCK_MAX_K}")
+        if self.A.m != self.A.n:
+            raise ValueError(f"CoupledBlockPCG needs a square matrix, got {self.A.m} x {self.A.n}")
+        if M is not None and not callable(getattr(M, "apply", None)):
+            raise TypeError("M must have apply(X, Y, stream=...) or be None")
+        self.K, self.M, self.stream = int(K), M, stream
+        m, dev = self.A.m, self.A.device
+        new = lambda: torch.zeros((m, self.K), dtype=torch.float64, device=dev)  # noqa: E731
+        self.X, self.R, self.P, self.Q = new(), new(), new(), new()
+        self.Z = self.R if M is None else new()
+        # K x K: rho (even iterations), rho (odd), Gamma, alpha, beta
+        self._sm = torch.zeros((5, self.K, self.K), dtype=torch.float64, device=dev)
+        self._rrbb = torch.zeros((2, self.K), dtype=torch.float64, device=dev)  # rr (with M, or gathered), bb
+        self._one = torch.ones(self.K, dtype=torch.float64, device=dev)
+        self._ws = torch.empty(gram_workspace_doubles(m, self.K, self.K), dtype=torch.float64, device=dev)
+        self._host = torch.empty((2, self.K), dtype=torch.float64).pin_memory()
+        self._par = 0  # which of the two rho buffers holds rho
+        self._graphs = None
+        self.iterations = 0
+        self.breakdown = False
+
+    def _rho(self, par: int) -> torch.Tensor:
+        return self._sm[par]
+
+    @property
+    def rr(self) -> torch.Tensor:
+        """R . R per column after the last iteration (on the device)."""
+        return self._rrbb[0] if self.M is not None else self._rho(self._par).diagonal()
+
+    @property
+    def bb(self) -> torch.Tensor:
+        """B . B per column of the last start() (on the device)."""
+        return self._rrbb[1]
+
+    def start(self, B: torch.Tensor, X0: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> None:
+        """R = B - A X0 (X0 None: X = 0, R = B, A is not launched), Z = M(R),
+        P = Z, rho = gram(Z, R), bb = coldot(B, B); asynchronous."""
+        s = stream if stream is not None else self.stream
+        m, K = self.A.m, self.K
+        _check_dense(B, m, K, "B")
+        with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+            self.R.copy_(B)
+            if X0 is None:
+                self.X.zero_()
+            else:
+                _check_dense(X0, m, K, "X0")
+                self.X.copy_(X0)
+                self.plan.run(self.X, self.Q, s)
+                col_axpy(self._one, None, self.Q, self.R, negate=True, stream=s)  # R = B - A X0
+            if self.M is not None:
+                self.M.apply(self.R, self.Z, stream=s)
+            self.P.copy_(self.Z)
+            self._par = 0
+            gram(self.Z, self.R, self._rho(0), s, self._ws)
+            coldot(B, B, self._rrbb[1], s, self._ws)
+        self.iterations = 0
+        self.breakdown = False
+
+    def iterate(self, n: int = 1, stream: torch.cuda.Stream | None = None) -> None:
+        """n iterations, launched back to back on `stream`: no host read, no
+        allocation, no synchronisation."""
+        s = stream if stream is not None else self.stream
+        gamma, alpha, beta = self._sm[2], self._sm[3], self._sm[4]
+        for _ in range(int(n)):
+            rho, rho_new = self._rho(self._par), self._rho(1 - self._par)
+            self.plan.run(self.P, self.Q, s)
+            gram(self.P, self.Q, gamma, s, self._ws)
+            small_solve(gamma, rho, alpha, s)
+            block_mul(self.P, alpha, self.X, self.X, stream=s)
+            block_mul(self.Q, alpha, self.R, self.R, negate=True, stream=s)
+            if self.M is not None:
+                self.M.apply(self.R, self.Z, stream=s)
+            gram(self.Z, self.R, rho_new, s, self._ws)
+            if self.M is not None:
+                coldot(self.R, self.R, self._rrbb[0], s, self._ws)
+            small_solve(rho, rho_new, beta, s)
+            block_mul(self.P, beta, self.Z, self.P, stream=s)
+            self._par = 1 - self._par
+        self.iterations += int(n)
+
+    def residuals(self, stream: torch.cuda.Stream | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """(rr, bb) on the host: one read of 2 K doubles, then a wait for it."""
+        s = stream if stream is not None else self.stream
+        with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+            if self.M is None:  # rr is the diagonal of the current rho: gathered beside bb
+                self._rrbb[0].copy_(self._rho(self._par).diagonal())
+            self._host.copy_(self._rrbb, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        h = self._host.numpy().copy()
+        return h[0], h[1]
+
+    def _capture(self, s) -> None:
+        """One graph per parity of the rho buffers, each of one iteration."""
+        side = s if s is not None else torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        par, its = self._par, self.iterations
+        self._graphs = {}
+        for p in (par, 1 - par):
+            g = torch.cuda.CUDAGraph()
+            assert self._par == p
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    self.iterate(1, side)
+            self._graphs[p] = g
+        self._par, self.iterations = par, its  # a capture executes nothing
+        torch.cuda.current_stream().wait_stream(side)
+
+    def solve(self, B: torch.Tensor, X0: torch.Tensor | None = None, tol: float = 1e-8, max_iters: int = 1000,
+              check_every: int = 1, graph: bool = False):
+        """Iterates until every column has rr[j] <= (tol * tol) * bb[j]
+        (evaluated in fp64 on the host from one read of 2 K doubles every
+        `check_every` iterations), max_iters is reached, or some rr is
+        non-finite (self.breakdown = True).  graph: replay captured
+        iterations instead of launching them.  Returns (X, the iteration
+        count, rr / bb per column as a numpy array; 0 for a zero right-hand
+        side met exactly)."""
+        if check_every < 1 or max_iters < 0:
+            raise ValueError("check_every must be at least 1 and max_iters non-negative")
+        s = self.stream
+        self.start(B, X0, s)
+        if graph and self._graphs is None:
+            self._capture(s)
+        rr = bb = None
+        while self.iterations < max_iters:
+            n = min(int(check_every), max_iters - self.iterations)
+            if graph:
+                with torch.cuda.stream(s if s is not None else torch.cuda.current_stream()):
+                    for _ in range(n):
+                        self._graphs[self._par].replay()
+                        self._par = 1 - self._par
+                self.iterations += n
+            else:
+                self.iterate(n, s)
+            rr, bb = self.residuals(s)
+            if not bool(np.all(np.isfinite(rr))):
+                self.breakdown = True
+                break
+            if bool(np.all(rr <= (tol * tol) * bb)):
+                break
+        if rr is None:
+            rel = np.full(self.K, np.nan)
+        else:
+            with np.errstate(all="ignore"):
+                rel = np.where(bb == 0.0, np.where(rr == 0.0, 0.0, np.inf), rr / bb)
+        return self.X, self.iterations, rel
+
+
 def spmm_rowblock(A: DeviceCSR, row_begin: int, row_end: int, X: torch.Tensor, Yblock: torch.Tensor,
                   stream=None) -> torch.Tensor:
     K = X.shape[1]
